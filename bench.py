@@ -7,9 +7,14 @@
 
 Workload = BASELINE.json configs[1]: ScanNet 2 cm voxels, batch_size 8 per GPU, ~150 k voxels per scene,
 synthetic scenes (box2mask_amd/synth.py), random-init weights, fp32.  One JSON line on rank 0.
-`roofline` is measured live with HIP events around every launch of the dominant kernel
-(b2m_conv_fwd: conv_fwd_flow_kernel, forward + data-gradient) inside the timed region; `cpu_baseline` times the CPU
-oracle (kind "port": MinkowskiEngine itself is unavailable) on a bounded sample on rank 0 at N=1.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`) and nothing else.
+`--full` adds everything else the benchmark measures, as separate passes after the timed steps: `roofline` (HIP events
+around every launch of the dominant kernel, b2m_conv_fwd: conv_fwd_flow_kernel, forward + data-gradient), the H2D-inclusive
+and read-every-loss repeats, the votes -> masks, inference and scene-preparation legs, `--features f16`, and `cpu_baseline`,
+which times the CPU oracle (kind "port": MinkowskiEngine itself is unavailable) on a bounded sample on rank 0 at N=1.
+The last timed step starts again from the seeded initial weights (restore_state), so what it computes is the same every run;
+`--dump-outputs DIR` writes that as DIR/*.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -133,6 +138,62 @@ def pairs_of(meta, cache, rb_lookup):
     return cache[key]
 
 
+def initial_state(model):
+    """(tensor, copy) of every parameter and buffer of the freshly made, seeded model."""
+    net = model.detection_model
+    return [(t, t.detach().clone()) for t in list(net.parameters()) + list(net.buffers())]
+
+
+def restore_state(initial, opt):
+    """The model and the optimiser as they were before the first step: the weights and BatchNorm statistics copied back in
+    place, Adam's moments and step counts zeroed (what a fresh Adam starts from).  Enqueued on the current stream, no host
+    read: a few multi-tensor launches, about 1 GB of device traffic.
+
+    bench.py runs it once, in front of the last timed step.  The default path's atomic reductions round differently from run
+    to run, and 2 + W + K - 1 Adam steps of a random-init network carry that far (the final loss of the headline command
+    varied from 5.1 to 5.8 over 13 runs); from the same weights, what one step computes differs by rounding only.  So the
+    last timed step -- the one --dump-outputs writes and `config.final_loss` reports -- computes the same every run."""
+    with torch.no_grad():
+        torch._foreach_copy_([t for t, _ in initial], [c for _, c in initial])
+        moments = [v for st in opt.state.values() for v in st.values() if torch.is_tensor(v)]
+        if moments:
+            torch._foreach_zero_(moments)
+
+
+DUMP_SAMPLE = 1 << 20   # elements kept per tensor by dump_outputs (the whole tensor when it is smaller)
+
+
+def dump_outputs(out_dir, losses, pred, model):
+    """What the last timed step computed, as out_dir/<name>.npy:
+    loss_<key>.npy -- every entry of the step's loss dict (float64 scalars);
+    pred_<head>.npy -- every head's output of the step's forward pass (rows x channels), float32;
+    bn_stats.npy   -- the BatchNorm running statistics the step left behind, float32, concatenated in named_buffers order.
+    A tensor of more than DUMP_SAMPLE elements is written as DUMP_SAMPLE of them at sorted positions drawn from a generator
+    seeded by its name (the per-voxel head of the S3DIS-shaped workload; the headline's are whole).  The step starts from the
+    seeded initial state (restore_state) on the same batch every run, so two runs -- or two builds -- write results that
+    differ by rounding only.  Not written: the gradients (the backward's atomic weight-gradient combines, carried through the
+    BatchNorm backward, move them by up to ~4e-3 of their largest element from run to run) and the updated weights (Adam's
+    first step moves a weight by lr * g / (|g| + eps): +-lr, with the sign of the gradients next to zero left to rounding)."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(name, t):
+        v = t.detach().reshape(-1).float()
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(v.numel(), DUMP_SAMPLE, replace=False))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        return v.cpu().numpy()
+    net = model.detection_model
+    arrays = {'loss_%s' % k: np.array(float(v.detach()) if torch.is_tensor(v) else float(v), np.float64) for k, v in losses.items()}
+    for h, t in pred.items():
+        a = sample(h, t)
+        arrays['pred_%s' % h] = a.reshape(t.shape) if a.size == t.numel() else a
+    arrays['bn_stats'] = np.concatenate([sample(k, b) for k, b in net.named_buffers() if b.is_floating_point()])
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -143,24 +204,35 @@ def main():
     ap.add_argument('--distinct-batches', type=int, default=4,
                     help='synthetic batches (different scenes, so different voxel counts and kernel maps) the steps cycle through, as '
                          'a data loader would deliver them; 1 = the same batch every step (rounds 1-5)')
-    ap.add_argument('--cpu-baseline', type=int, default=1, help='0 disables the CPU oracle timing')
-    ap.add_argument('--cpu-voxels', type=int, default=150_000, help='voxels per scene of the CPU baseline sample (default: the metric\'s scene size)')
-    ap.add_argument('--cpu-scenes', type=int, default=1, help='scenes in the CPU baseline sample')
-    ap.add_argument('--detail', type=int, default=0, help='1 prints a per-layer-shape table of the conv launches to stderr')
-    ap.add_argument('--cpu-timeout', type=int, default=240, help='seconds after which the CPU baseline is abandoned')
-    ap.add_argument('--votes', type=int, default=1, help='0 skips the votes -> instance masks leg (outside the timed steps)')
-    ap.add_argument('--inference', type=int, default=1, help='0 skips the batch-size-1 inference leg (outside the timed steps)')
-    ap.add_argument('--prepare', type=int, default=1, help='0 skips the raw points -> device batch leg (outside the timed steps)')
+    ap.add_argument('--cpu-baseline', type=int, default=1, help='--full: 0 disables the CPU oracle timing (a plain run has none)')
+    ap.add_argument('--cpu-voxels', type=int, default=150_000, help='--full: voxels per scene of the CPU baseline sample (default: the metric\'s scene size)')
+    ap.add_argument('--cpu-scenes', type=int, default=1, help='--full: scenes in the CPU baseline sample')
+    ap.add_argument('--detail', type=int, default=0, help='--full only: 1 prints a per-layer-shape table of the conv launches to stderr')
+    ap.add_argument('--cpu-timeout', type=int, default=240, help='--full: seconds after which the CPU baseline is abandoned')
+    ap.add_argument('--votes', type=int, default=1, help='--full: 0 skips the votes -> instance masks leg (outside the timed steps; a plain run has none)')
+    ap.add_argument('--inference', type=int, default=1, help='--full: 0 skips the batch-size-1 inference leg (outside the timed steps; a plain run has none)')
+    ap.add_argument('--prepare', type=int, default=1, help='--full: 0 skips the raw points -> device batch leg (outside the timed steps; a plain run has none)')
     ap.add_argument('--features', default='f32', choices=['f32', 'f16'],
-                    help="f16 adds the `inference_f16` object: the batch-size-1 inference leg with the HALF trunk (activations in "
+                    help="--full only: f16 adds the `inference_f16` object: the batch-size-1 inference leg with the HALF trunk (activations in "
                          "HBM as IEEE half, f16 MFMA, fp32 accumulation; BASELINE configs[4]).  Never the headline, never the default")
     ap.add_argument('--side-passes', type=int, default=1,
-                    help='0 skips the H2D-inclusive and the read-every-loss repeats of the timed steps (value_incl_h2d / value_sync_per_step '
-                         'become null): the two-rank rehearsal of the test suite')
+                    help='--full: 0 skips the H2D-inclusive and the read-every-loss repeats of the timed steps (value_incl_h2d / value_sync_per_step '
+                         'become null; a plain run has neither): the two-rank rehearsal of the test suite')
     ap.add_argument('--workload', default='scannet', choices=['scannet', 's3dis', 'arkit'],
                     help='scannet = BASELINE configs[1] (the headline); s3dis / arkit = configs[4] / [5], own lines under profiles/, '
                          'never the headline')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, every other figure: CPU baseline and parity, roofline passes, H2D-inclusive and '
+                         'read-every-loss repeats, the votes / inference / prepare legs, --features f16 (the options above that '
+                         'select them act only with --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (its losses, the heads\' outputs, the BatchNorm statistics) as '
+                         'DIR/<name>.npy; that step starts from the seeded initial weights, so runs agree to rounding')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full and (args.features != 'f32' or args.detail):
+        ap.error('--features f16 and --detail 1 are figures of --full')
     # host-side torch ops (the outputs' clamp, pred2mask's bookkeeping on CPU tensors): the thread count the CPU baseline uses,
     # set whether or not that leg runs (with the default -- every core of the box -- a 2 k-element op costs milliseconds)
     try:
@@ -179,18 +251,23 @@ def main():
 
     # The CPU baseline runs FIRST, before this process touches the GPU (pure torch-CPU oracle, rank 0, N=1 only).
     cpu_result = cpu_keep = None
-    if args.cpu_baseline and int(os.environ.get('WORLD_SIZE', '1')) == 1:
+    if args.full and args.cpu_baseline and int(os.environ.get('WORLD_SIZE', '1')) == 1:
         cpu_result, cpu_keep = cpu_baseline(args.cpu_scenes, args.cpu_voxels, args.cpu_timeout, args.target_voxels)
 
-    from box2mask_amd import _lib, synth
+    from box2mask_amd import _lib
     from box2mask_amd import sparse as sparse_mod
-    from box2mask_amd.config import scannet_config
     from box2mask_amd.model import Model
     from box2mask_amd.parallel import init_distributed
+
+    # the synthetic batches of this rank, also before any GPU call (their scenes are made in child processes); the rank
+    # and world size are those init_distributed reads from the environment
+    rank_env, world_env = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
+    workload, cfg, tables, batches = make_workload(args, rank_env, world_env, parallel=True)
 
     rank, world = init_distributed()
     if world != args.gpus:
         sys.exit('bench.py: started as %d rank(s) but --gpus %d' % (world, args.gpus))
+    assert (rank, world) == (rank_env, world_env), ((rank, world), (rank_env, world_env))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if os.environ.get('B2M_BENCH_ONE_DEVICE') == '1':      # rehearsal of the N > 1 path on a one-GPU box (with B2M_DIST_BACKEND=gloo)
         local = 0
@@ -205,21 +282,11 @@ def main():
     torch.manual_seed(1234)
 
     backend = dist.get_backend() if (dist.is_available() and dist.is_initialized()) else None
-    workload, cfg, tables, batch = make_workload(args, rank, world)
-    # further batches of the same shape, other scenes (scannet only: the other workloads are four fixed scene sizes): the steps
-    # cycle through them, so allocation sizes, rulebook shapes and tile counts differ from step to step like a loader's
-    batches = [batch]
-    if args.workload == 'scannet':
-        t_more = time.time()
-        # (a loader's batches differ by some per cent in size: 1.0 / 0.93 / 1.07 / 1.0 x the metric's scene size -- mean 1.0)
-        jitter = (1.0, 0.93, 1.07, 1.0)
-        for j in range(1, max(1, args.distinct_batches)):
-            batches.append(synth.make_batch(args.batch_size, seed0=(j * world + rank) * args.batch_size,
-                                            target_voxels=int(args.target_voxels * jitter[j % 4])))
-        workload['gen_s'] += time.time() - t_more
+    batch = batches[0]
     model = Model(cfg, *tables, device=dev)
     opt = torch.optim.Adam(model.parameters(), lr=cfg.lr, fused=True)      # same update as training.py:35, one kernel
     model.train()
+    initial = initial_state(model)      # the seeded weights the last timed step starts from again (restore_state)
 
     # ---- synthetic batch of this rank (weak scaling: every rank gets batch_size scenes), resident in HBM
     t0 = time.time()
@@ -233,26 +300,28 @@ def main():
     torch.cuda.synchronize()
     gen_s = workload['gen_s'] + time.time() - t0
 
-    # keep every rulebook built during the timed steps reachable for the FLOP accounting
+    # keep every rulebook built during the timed steps reachable for the FLOP accounting (--full)
     rb_lookup = {}
-    orig_init = sparse_mod.Rulebook.__init__
+    if args.full:
+        orig_init = sparse_mod.Rulebook.__init__
 
-    # (only the pair-count array of a rulebook is kept -- K x ntiles ints; keeping the rulebooks themselves alive pinned
-    # ~1 GB per step: the pair lists of the 125-offset map alone are 750 MB, so a 45-step run allocated fresh memory in
-    # every step and reported 30.6 GB of `peak_mem_gb` for a step that needs a third of it)
-    def rb_init(self, *a, **k):
-        orig_init(self, *a, **k)
-        rb_lookup[self.rb_cnt.data_ptr()] = (self.rb_cnt, self.K, self.ntiles)
-    sparse_mod.Rulebook.__init__ = rb_init
+        # (only the pair-count array of a rulebook is kept -- K x ntiles ints; keeping the rulebooks themselves alive pinned
+        # ~1 GB per step: the pair lists of the 125-offset map alone are 750 MB, so a 45-step run allocated fresh memory in
+        # every step and reported 30.6 GB of `peak_mem_gb` for a step that needs a third of it)
+        def rb_init(self, *a, **k):
+            orig_init(self, *a, **k)
+            rb_lookup[self.rb_cnt.data_ptr()] = (self.rb_cnt, self.K, self.ntiles)
+        sparse_mod.Rulebook.__init__ = rb_init
 
     # HIP events cost device and host time (about 2.5 % of a step when every conv and BN launch is bracketed), and in the
     # timed region the weight gradients run on a second stream BESIDE the data gradients: a bracketed launch's duration is
     # then the time it shared the chip, not the kernel's own.  So the timed region brackets the dominant kernel only
     # (b2m_conv_fwd: `roofline_timed_region`, as it ran), and K more steps AFTER the H2D-inclusive repeat run with the side
     # stream off and all three kernels bracketed (`roofline`, `roofline_wgrad`, `roofline_bn_apply`: every kernel alone on
-    # the chip, which is what a roofline fraction is about).
+    # the chip, which is what a roofline fraction is about).  A plain run (no --full) brackets nothing.
     timer = LaunchTimer(['b2m_conv_fwd', 'b2m_conv_fwd_stats', 'b2m_conv_up'])
-    _lib.set_hook(timer.hook)
+    if args.full:
+        _lib.set_hook(timer.hook)
 
     # Model.prefetch: the NEXT batch's sparse tensor (Morton order, coordinate hash, 7 strided + 16 kernel maps) is built
     # on a second stream while this step's network runs, as a training loop with a data loader one batch ahead would do.
@@ -261,6 +330,7 @@ def main():
     PREFETCH_AT = os.environ.get('B2M_BENCH_PREFETCH_AT', 'now')
     prefetch_on = [True]
     cursor = [0]                        # steps taken: step i trains on cycle[i % len(cycle)] and prefetches the one after it
+    last_pred = [None]                  # the head outputs of the latest step (--dump-outputs)
     cycle = [batches]                   # (the H2D pass swaps in the pinned-host forms of the same batches)
 
     def step():
@@ -275,7 +345,7 @@ def main():
         if PREFETCH_AT == 'forward':
             ev0 = torch.cuda.Event()
             ev0.record()                # the device reaches this point when the step's forward pass begins
-        losses = model.compute_loss(cur_b, 150)
+        losses, last_pred[0] = model.compute_loss_detection(cur_b, 150)     # (Model.compute_loss without dropping the heads' outputs)
         if PREFETCH and prefetch_on[0]:
             # ready=True: the next batch's tensors were complete before this step was enqueued (device tensors from setup, or the
             # pinned host buffers of the H2D pass) -- the side stream starts at once, i.e. wherever the device is while the host
@@ -303,7 +373,7 @@ def main():
     # TIMED_EVERY-th step only (default 5: steps 2, 7, 12, ...): two events per launch on 199 launches cost the step 1.5-2 %
     # (the H2D-inclusive repeat, which carries none, used to come out FASTER than the headline: 117.0 against 114.8 scenes/s),
     # and the headline should not pay for its own instrumentation.  B2M_BENCH_TIMED_EVENTS=1: every step (rounds 1-5); 0: none.
-    TIMED_EVERY = int(os.environ.get('B2M_BENCH_TIMED_EVENTS', '5'))
+    TIMED_EVERY = int(os.environ.get('B2M_BENCH_TIMED_EVENTS', '5')) if args.full else 0
     timed_steps_sampled = 0
     from box2mask_amd import functional as F_
     cstat = F_.collective_stats
@@ -312,6 +382,8 @@ def main():
     for i_ in range(args.steps):
         timer.enabled = TIMED_EVERY > 0 and i_ % TIMED_EVERY == min(TIMED_EVERY // 2, args.steps - 1)
         timed_steps_sampled += int(timer.enabled)
+        if i_ == args.steps - 1:
+            restore_state(initial, opt)
         losses = step()
     torch.cuda.synchronize()
     if world > 1:
@@ -319,11 +391,14 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
     timer.enabled = False
-    # collectives of the timed steps (N > 1; zeros for a single process), and one more step with an event pair around every
-    # SyncBN all-reduce: what the latency-bound exchanges cost on this fabric (they are blocking on the compute stream)
+    # collectives of the timed steps (N > 1; zeros for a single process), and with --full one more step with an event pair
+    # around every SyncBN all-reduce: what the latency-bound exchanges cost on this fabric (they are blocking on the compute
+    # stream).  The outputs are written before that step changes the weights.
     collectives = {'syncbn_all_reduces_per_step': cstat['syncbn'] / args.steps, 'gradient_buckets_per_step': cstat['grad_buckets'] / args.steps,
                    'bytes_per_step': cstat['bytes'] // args.steps}
-    if world > 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, last_pred[0], model)
+    if world > 1 and args.full:
         cstat['timing'] = True
         cstat['events'] = []
         step()
@@ -340,6 +415,32 @@ def main():
         elapsed = float(t.item())
     loss_val = float(losses['optimization_loss'].item())
     peak_mem_gb = torch.cuda.max_memory_allocated(dev) / 2 ** 30
+    scenes = world * workload['batch_size'] * args.steps
+    result = {
+        'metric': workload['metric'], 'value': round(scenes / elapsed, 3), 'unit': 'scenes/s',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(elapsed / args.steps * 1e3, 2), 'higher_is_better': True, 'scaling': 'weak',
+        'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        # the reference's README quotes "~48GB GPURAM" for this batch size on MinkowskiEngine
+        'peak_mem_gb': round(peak_mem_gb, 2),
+        'config': {'workload': workload['name'],
+                   'global_batch': world * workload['batch_size'], 'voxels_per_scene': n_vox // workload['batch_size'],
+                   # what the process group saw (RCCL is backend "nccl" on ROCm); None / 1 for a single process
+                   'backend': backend, 'ranks_seen': (dist.get_world_size() if backend else 1),
+                   'voxels_per_gpu_batch': n_vox, 'parallelism': 'dp%d' % world, 'final_loss': round(loss_val, 4),
+                   # the steps cycle through this many different batches (sizes jitter like a loader's); their voxel counts
+                   'distinct_batches': len(batches), 'voxels_of_batches': vox_of_batches,
+                   'scene_gen_s': round(gen_s, 1), 'setup_steps': SETUP_STEPS,
+                   'prefetch': ('next batch: coordinate + kernel maps on a second stream during the step'
+                                if PREFETCH else 'off'),
+                   'collectives': collectives,
+                   'steps_executed': SETUP_STEPS + args.warmup + args.steps, 'full': args.full}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+        return
 
     # ---- the same K steps with the batch handed over as pinned HOST buffers (SURVEY 8d defines the metric with the
     # H2D copy; `value` stays the HBM-resident rate, this one is reported beside it)
@@ -554,7 +655,6 @@ def main():
                 'gflop_per_step': round(a['flops'] / max(args.steps, 1) / 1e9, 2),
                 'ms_per_step': round(ms_step, 3)}
 
-    scenes = world * workload['batch_size'] * args.steps
     fwd = agg.get('b2m_conv_fwd', dict(ms=0.0, flops=0.0, launches=0))
     wg = agg.get('b2m_conv_wgrad', dict(ms=0.0, flops=0.0, launches=0))
     roofline = roof(fwd, 'conv_fwd_kernel')
@@ -594,34 +694,11 @@ def main():
     roofline_wgrad['clock_mhz'] = roofline['clock_mhz']
     roofline_wgrad['kernel'] = 'b2m_conv_wgrad: conv_wgrad_flow_kernel (+ conv_wgrad_kernel for single-block narrow heads)'
 
-    value = scenes / elapsed
-    result = {
-        'metric': workload['metric'], 'value': round(value, 3), 'unit': 'scenes/s',
-        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': round(elapsed / args.steps * 1e3, 2), 'higher_is_better': True, 'scaling': 'weak',
-        'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+    result.update({
         # the same steps with the batch arriving in pinned host memory (PCIe copy inside the timed region)
         'value_incl_h2d': round(scenes / elapsed_h2d, 3) if elapsed_h2d else None, 'h2d_mb_per_step': round(h2d_bytes / 1e6, 1),
         # every loss `.item()`-ed in every iteration, as training.py:170-174 does (the host cannot run ahead)
         'value_sync_per_step': round(scenes / elapsed_sync, 3) if elapsed_sync else None,
-        # /root/reference/README.md:102 quotes "~48GB GPURAM" for this batch size on MinkowskiEngine
-        'peak_mem_gb': round(peak_mem_gb, 2),
-        'config': {'workload': workload['name'],
-                   'global_batch': world * workload['batch_size'], 'voxels_per_scene': n_vox // workload['batch_size'],
-                   # what the process group saw (RCCL is backend "nccl" on ROCm); None / 1 for a single process
-                   'backend': backend, 'ranks_seen': (dist.get_world_size() if backend else 1),
-                   'voxels_per_gpu_batch': n_vox, 'parallelism': 'dp%d' % world, 'final_loss': round(loss_val, 4),
-                   # the steps cycle through this many different batches (sizes jitter like a loader's); their voxel counts
-                   'distinct_batches': len(batches), 'voxels_of_batches': vox_of_batches,
-                   # the SURVEY 8d form of the metric (H2D copy of the batch inside the step) next to `value` -- kept here too
-                   # because the driver's record carries `config` in full
-                   'value_incl_h2d': round(scenes / elapsed_h2d, 3) if elapsed_h2d else None,
-                   'h2d_mb_per_step': round(h2d_bytes / 1e6, 1),
-                   'scene_gen_s': round(gen_s, 1), 'setup_steps': SETUP_STEPS,
-                   'prefetch': ('next batch: coordinate + kernel maps on a second stream during the step'
-                                if PREFETCH else 'off'),
-                   'collectives': collectives,
-                   'steps_executed': SETUP_STEPS + args.warmup + (4 if args.side_passes else 2) * args.steps + (3 if args.side_passes else 1) + (1 if world > 1 else 0)},
         'train_f16': train_f16,
         'roofline': roofline, 'roofline_timed_region': roofline_timed, 'roofline_wgrad': roofline_wgrad,
         # an HBM-bound kernel of the path, same live HIP-event method: BatchNorm apply (+residual, +ReLU) streams
@@ -634,7 +711,13 @@ def main():
                               'algorithmic_bytes': round(hbm['bytes'] / max(hbm['launches'], 1)),
                               'launches_per_step': hbm['launches'] // max(args.steps, 1),
                               'kernel': 'bn_apply_kernel'},
-    }
+    })
+    result['config'].update({
+                   # the SURVEY 8d form of the metric (H2D copy of the batch inside the step) next to `value` -- kept here too
+                   # because the driver's record carries `config` in full
+                   'value_incl_h2d': round(scenes / elapsed_h2d, 3) if elapsed_h2d else None,
+                   'h2d_mb_per_step': round(h2d_bytes / 1e6, 1),
+                   'steps_executed': SETUP_STEPS + args.warmup + (4 if args.side_passes else 2) * args.steps + (3 if args.side_passes else 1) + (1 if world > 1 else 0)})
 
     # ---- second half of configs[1] ("+ iou_nms on HIP"): votes -> instance masks of the same 8 scenes, reported
     # beside the headline value (never part of it)
@@ -666,18 +749,56 @@ def main():
         dist.barrier()
 
 
-def make_workload(args, rank, world):
-    """(description, cfg, class tables, host batch) of this rank.  scannet = BASELINE configs[1], the headline.  The other
+def _scene(job):
+    from box2mask_amd import synth
+    seed, kw = job
+    return synth.make_scene(seed, **kw)
+
+
+def make_scenes(jobs, world=1, parallel=False):
+    """[synth.make_scene(seed, **kw) for seed, kw in jobs].  parallel: the scenes made side by side in fresh child processes (at
+    most 16 over the ranks of the node; a 150 k-voxel scene is about a second of numpy, and a headline run needs 32 of them).
+    Each scene draws from its own seeded generator: the result is the serial loop's, bit for bit.  Only bench.main asks for
+    it: the children of a `spawn` pool import the caller's main module again, which a script without a __main__ guard cannot
+    survive."""
+    if not parallel:
+        return [_scene(j) for j in jobs]
+    try:
+        avail = len(os.sched_getaffinity(0))
+    except AttributeError:
+        avail = os.cpu_count() or 1
+    n = max(1, min(len(jobs), 16 // max(world, 1), avail))
+    if n == 1:
+        return [_scene(j) for j in jobs]
+    import concurrent.futures
+    import multiprocessing
+    with concurrent.futures.ProcessPoolExecutor(n, mp_context=multiprocessing.get_context('spawn')) as ex:
+        return list(ex.map(_scene, jobs))
+
+
+def make_workload(args, rank, world, parallel=False):
+    """(description, cfg, class tables, host batches) of this rank (parallel: the scenes made in child processes, make_scenes).  scannet = BASELINE configs[1], the headline.  The other
     two are BASELINE configs[4] / [5] as bench lines of their own (profiles/r03_workload_*.json), never the headline:
     s3dis -- configs/s3dis_fold5.txt: batch 4, 13 classes, per-voxel semantics head beside the segment heads, rooms of
     0.25-0.6 M voxels (S3DIS rooms after the reference's 0.25 point sampling); arkit -- configs/arkitscenes.txt: batch 4,
-    4 cm voxels, 28 classes, mixed scene sizes, features handed over as fp16 (upcast at the boundary)."""
+    4 cm voxels, 28 classes, mixed scene sizes, features handed over as fp16 (upcast at the boundary).
+    scannet has `--distinct-batches` batches of the same shape, other scenes: the steps cycle through them, so allocation sizes,
+    rulebook shapes and tile counts differ from step to step like a loader's; the other workloads are one batch of four fixed
+    scene sizes."""
     from box2mask_amd import synth
     from box2mask_amd.config import scannet_config
     t0 = time.time()
     if args.workload == 'scannet':
         cfg = scannet_config(multigpu=(world > 1), batch_size=args.batch_size)
-        batch = synth.make_batch(args.batch_size, seed0=rank * args.batch_size, target_voxels=args.target_voxels)
+        bs = args.batch_size
+        # (a loader's batches differ by some per cent in size: 1.0 / 0.93 / 1.07 / 1.0 x the metric's scene size -- mean 1.0;
+        # batch j holds the scenes synth.make_batch(bs, seed0=(j * world + rank) * bs) makes)
+        jitter = (1.0, 0.93, 1.07, 1.0)
+        nb = max(1, args.distinct_batches)
+        jobs = [((j * world + rank) * bs + s, dict(target_voxels=int(args.target_voxels * jitter[j % 4]) if j else args.target_voxels))
+                for j in range(nb) for s in range(bs)]
+        items = make_scenes(jobs, world, parallel)
+        batches = [synth.collate(items[j * bs:(j + 1) * bs]) for j in range(nb)]
         w = dict(name='ScanNet 2cm voxels, batch_size=%d per GPU, sparse-conv fwd/bwd + losses + Adam '
                       '(BASELINE configs[1])' % args.batch_size,
                  metric='ScanNet scenes/sec (fwd+bwd, ~150k voxels @2cm)', batch_size=args.batch_size)
@@ -686,7 +807,7 @@ def make_workload(args, rank, world):
         cfg = scannet_config(multigpu=(world > 1), batch_size=4, eval_ths=[0.5, 0.03, 0.3, 0.6], loss_weight_bb_scores=3.0,
                              network_heads=['mlp_offsets', 'mlp_bounds', 'mlp_bb_scores', 'mlp_per_vox_semantics'])
         sizes = [250_000, 400_000, 600_000, 350_000]
-        items = [synth.make_scene(rank * 4 + i, target_voxels=tv) for i, tv in enumerate(sizes)]
+        items = make_scenes([(rank * 4 + i, dict(target_voxels=tv)) for i, tv in enumerate(sizes)], world, parallel)
         batch = synth.collate(items)
         n = batch['vox_coords'].shape[0]
         batch['gt_semantics'] = batch['gt_semantics'] % 13
@@ -701,8 +822,8 @@ def make_workload(args, rank, world):
         cfg = scannet_config(multigpu=(world > 1), batch_size=4, eval_ths=[0.5, 0.05, 0.4, 0.6], loss_weight_bb_scores=3.0,
                              loss_weight_semantics=0.3, voxel_size=0.04)
         sizes = [30_000, 200_000, 80_000, 120_000]
-        items = [synth.make_scene(rank * 4 + 10 + i, target_voxels=tv, voxel_size=0.04, pts_per_m2=5000.0)
-                 for i, tv in enumerate(sizes)]
+        items = make_scenes([(rank * 4 + 10 + i, dict(target_voxels=tv, voxel_size=0.04, pts_per_m2=5000.0))
+                             for i, tv in enumerate(sizes)], world, parallel)
         batch = synth.collate(items)
         batch['gt_semantics'] = torch.from_numpy(ids[batch['gt_semantics'].numpy() % len(ids)])
         batch['vox_features'] = batch['vox_features'].half()
@@ -712,8 +833,10 @@ def make_workload(args, rank, world):
         w = dict(name='ARKitScenes-shaped scenes (%s voxels @4cm), batch_size=4 per GPU, 28 classes, fp16 features in '
                       '(BASELINE configs[5], configs/arkitscenes.txt)' % '/'.join('%dk' % (v // 1000) for v in sizes),
                  metric='ARKit-shaped scenes/sec (fwd+bwd, 30-200 k voxels @4cm)', batch_size=4)
+    if args.workload != 'scannet':
+        batches = [batch]
     w['gen_s'] = time.time() - t0
-    return w, cfg, tables, batch
+    return w, cfg, tables, batches
 
 
 def gpu_vs_oracle(keep, dev):

@@ -18,7 +18,7 @@ def test_bench_two_ranks_rehearsal():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--batch-size', '2', '--target-voxels', '20000', '--cpu-baseline', '0', '--side-passes', '0'],
+                        '--batch-size', '2', '--target-voxels', '20000', '--cpu-baseline', '0', '--side-passes', '0', '--full'],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
@@ -26,7 +26,7 @@ def test_bench_two_ranks_rehearsal():
     d = json.loads(lines[0])
     assert d['n_gpus'] == 2 and d['config']['global_batch'] == 4 and d['config']['parallelism'] == 'dp2'
     assert d['value'] > 0 and d['scaling'] == 'weak' and 'votes_to_masks' not in d
-    # the collectives of a step are counted (and the SyncBN exchanges timed): what an 8-GPU lease will show first
+    # the collectives of a step are counted (and, with --full, the SyncBN exchanges timed): what an 8-GPU lease will show first
     c = d['config']['collectives']
     assert c['syncbn_all_reduces_per_step'] >= 100 and c['gradient_buckets_per_step'] >= 1 and c['syncbn_ms_per_step'] > 0
     assert c['syncbn_timed'] == c['syncbn_all_reduces_per_step']

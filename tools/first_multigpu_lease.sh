@@ -26,11 +26,11 @@ for ipc in 0 1; do
     port=$((port + 1))
     log=$out/bench_n${n}_ipc${ipc}
     if [ "$n" = 1 ]; then
-      B2M_SYNCBN_IPC=$ipc timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-baseline 0 --votes 0 --inference 0 --prepare 0 \
+      B2M_SYNCBN_IPC=$ipc timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-baseline 0 --votes 0 --inference 0 --prepare 0 \
           > $log.json 2> $log.err || { tail -20 $log.err; exit 1; }
     else
       B2M_SYNCBN_IPC=$ipc timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port \
-          bench.py --gpus $n --steps 20 --warmup 5 > $log.json 2> $log.err || { tail -20 $log.err; exit 1; }
+          bench.py --gpus $n --steps 20 --warmup 5 --full > $log.json 2> $log.err || { tail -20 $log.err; exit 1; }
     fi
   done
 done

@@ -6,8 +6,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from box2mask_amd.model import Model
-args = argparse.Namespace(workload=os.environ.get('WORKLOAD', 'arkit'), batch_size=8, target_voxels=150000)
-w, cfg, tables, batch = bench.make_workload(args, 0, 1)
+args = argparse.Namespace(workload=os.environ.get('WORKLOAD', 'arkit'), batch_size=8, target_voxels=150000, distinct_batches=1)
+w, cfg, tables, batches = bench.make_workload(args, 0, 1)
+batch = batches[0]
 cfg.half_training = os.environ.get('HALF', '0') == '1'
 model = Model(cfg, *tables)
 opt = torch.optim.Adam(model.parameters(), lr=cfg.lr, fused=True)

@@ -26,7 +26,7 @@ def load(path):
 def main():
     fetch, write = load(sys.argv[1]), load(sys.argv[2])
     out = {'_units': 'bytes per launch; fetch = 2 x FETCH_SIZE x 1024 (gfx950 correction), write = WRITE_SIZE x 1024',
-           '_source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python3 bench.py --steps 1 --warmup 1 '
+           '_source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python3 bench.py --full --steps 1 --warmup 1 '
                       '--cpu-baseline 0 --votes 1 --prepare 0 (two passes)'}
     # calibration of the x2: bn_apply2_kernel streams two tensors in and one of the same size out (WRITE_SIZE is exact), so
     # raw FETCH_SIZE / WRITE_SIZE = 1.0 when FETCH_SIZE counts half the streamed bytes (2.0 if it counted all of them)
