@@ -92,6 +92,10 @@ PROTOTYPES = {
     'b2m_mask_hist': [P, I64, I32, P, I64, I32, P, P],
     'b2m_mask_pack': [P, I32, I64, P, I64, P],
     'b2m_set_ious': [P, P, I64, P, P],
+    'b2m_mask_hulls': [P, I64, I32, P, I64, P, P, P, I32, P, P, P, P, P, P, P],
+    'b2m_obb_corners': [P, P, P, I32, P, P],
+    'b2m_hull_box_iou': [P, P, P, P, I32, P, P, I32, P, P],
+    'b2m_aabb_iou': [P, P, I32, P, P, P, I32, P, P],
     # include/b2m_prepare.h
     'b2m_vox_shift': [P, I64, P, P, P],
     'b2m_unique_insert_async': [P, I64, P, I64, P, P, P, P],

@@ -585,6 +585,55 @@ int b2m_mask_gather_batch(const int64_t* desc, int32_t n_scenes, int64_t total_k
 int b2m_mask_gather_batch_t(const int64_t* desc, int32_t n_scenes, int64_t total_kept, int64_t max_pts, int64_t max_words,
                             const int64_t* tbits, void* stream);
 
+/* ---------------------------------------------------------------- detection boxes (ARKitScenes oriented-box mAP)
+ * The device half of Evaluater.arkitscenes_eval (models/evaluation.py:245-316): a prism per predicted mask (convex hull of the
+ * mask's points in x-y, extruded over their z range, :280-292), the corners of every ground-truth box (utils/box_util.py:360-384)
+ * and box3d_iou (utils/box_util.py:101-140) / calc_iou (utils/metric_util.py:91-113) of the pairs.  All fp64.  The matching and
+ * the VOC AP over the resulting table are host code (box2mask_amd/eval_detection.py). */
+
+#define B2M_HULL_MAX 512            /* capacity of one row's hull, in vertices */
+#define B2M_HULL_CHUNKS 32          /* `work` of b2m_mask_hulls: k * B2M_HULL_CHUNKS * B2M_HULL_PART doubles */
+#define B2M_HULL_PART 56
+#define B2M_HULL_FLAG_VERTICES 1    /* flags[r]: the hull has more than B2M_HULL_MAX vertices (n_hull[r] = how many; none written) */
+#define B2M_HULL_FLAG_CANDIDATES 2  /* flags[r]: more than `cap` hull candidates (ncand[r] = how many; call again with cap >= that) */
+#define B2M_OBB_REC 16              /* doubles per ground-truth box record of b2m_obb_corners */
+
+/* For each of k bit rows (bits[k][words], the layout of b2m_mask_pack) over the n points pos[n][3]:
+ *   count[r]   number of set points            box6[r][6]  min x,y,z then max x,y,z of them (zmin = [2], zmax = [5])
+ *   hull[r][B2M_HULL_MAX][2], n_hull[r]   the vertices of the convex hull of the row's points projected on x-y: counter-clockwise,
+ *       starting at the lexicographically smallest (x, y), no repeated and no collinear-interior vertex.  Vertices are input
+ *       coordinates bit for bit; the turn test is the fp64 cross product.  Fewer than 3 distinct projected points, or all of them
+ *       collinear: the 1 or 2 extreme points (zero area for b2m_hull_box_iou).  An empty row: n_hull = 0 and an inverted box6.
+ *   flags[r]   0, or B2M_HULL_FLAG_* : the row's hull is NOT reported (never truncated).
+ * Three passes, no host read: (1) per (row, chunk of words) the count, the box and the extreme point along 16 fixed directions
+ * (zero words skipped, wave then LDS reductions, largest dot / smallest point index: independent of the order); (2) the points
+ * not strictly inside the polygon of those extremes -- the only possible hull vertices -- appended to cand[r] (integer atomics
+ * on ncand[r] only); (3) per row a bitonic sort of the candidates by (x, y) and Andrew's monotone chain.
+ * Scratch: work (see B2M_HULL_CHUNKS), cand double[k][cap][2], stk int32[k][cap], ncand int32[k]; cap a power of two >= 64. */
+int b2m_mask_hulls(const uint64_t* bits, int64_t words, int32_t k, const double* pos, int64_t n, double* work, double* cand,
+                   int32_t* stk, int32_t cap, int32_t* ncand, int32_t* count, double* box6, double* hull, int32_t* n_hull,
+                   int32_t* flags, void* stream);
+
+/* Ground-truth boxes: centers[g][3], bounds[g][3] (half sizes), rotations[g][9] as labels['per_instance_bb_rotations'] stores
+ * them (the corners use the TRANSPOSE of the row-major 3x3, evaluation.py:261).  boxes[g][B2M_OBB_REC]:
+ *   0..7 x,y of corners 0..3 of get_oriented_corners    8 z of corner 0    9 z of corner 7    10 box3d_vol (box_util.py:87-92)
+ *   11..13 get_rotated_bounds(...) * 2 (box_util.py:339-357: the axis-aligned size)    14, 15 zero */
+int b2m_obb_corners(const double* centers, const double* bounds, const double* rotations, int32_t g, double* boxes, void* stream);
+
+/* iou[r*g + b] = box3d_iou(prism of hull row r, box b) where pcls[r] == gcls[b] >= 0, else 0: Sutherland-Hodgman clip of the hull
+ * by the four rectangle edges with the reference's strict `inside` ((cp2-cp1) x (p-cp1) > 0, box_util.py:31-32) and its
+ * intersection formula, shoelace areas, z overlap max(0, min(zmax, z7) - max(zmin, z0)), vol1 = hull area * (zmax - zmin),
+ * vol2 = box3d_vol.  An empty or degenerate (< 3 vertices) intersection, a hull of fewer than 3 vertices or a flagged row: 0.
+ * A rectangle whose corners 0..3 run CLOCKWISE clips everything away in the reference (same predicate): 0 here as well.
+ * hull / n_hull / box6 as b2m_mask_hulls wrote them, boxes as b2m_obb_corners. */
+int b2m_hull_box_iou(const double* hull, const int32_t* n_hull, const double* box6, const int32_t* pcls, int32_t k,
+                     const double* boxes, const int32_t* gcls, int32_t g, double* iou, void* stream);
+
+/* The oriented_boxes=False variant: prediction = (centre, size) of box6 (evaluation.py:294-298), ground truth = (gcenters[b],
+ * boxes[b][11..13]); iou[r*g + b] = calc_iou where the classes agree, else 0. */
+int b2m_aabb_iou(const double* box6, const int32_t* pcls, int32_t k, const double* gcenters, const double* boxes,
+                 const int32_t* gcls, int32_t g, double* iou, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -622,10 +622,193 @@ def gen_eval():
     print('eval_metric.npz: mAP %.4f  AP50 %.4f  AP25 %.4f' % tuple(out['all_ap']))
 
 
+def _savez_fixed(path, arrays):
+    """np.savez_compressed with fixed member timestamps: the same arrays give the same bytes on every run."""
+    import zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, 'w') as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+ARKIT_IDS = [3, 4, 5, 6, 7, 15, 24, 34]
+
+
+def detection_scene(rng, si):
+    """One synthetic ARKit-shaped room: oriented (yaw-only) ground-truth boxes filled with points, background clutter, and byte
+    masks that cover the boxes to varying degrees.  Positions are float32 values (the fixture stores them as such)."""
+    g = 9 + si
+    centers = np.stack([rng.uniform(0.5, 7.5, g), rng.uniform(0.5, 5.5, g), rng.uniform(0.3, 1.2, g)], 1)
+    centers[:, :2] = (np.arange(g)[:, None] * [1.7, 1.1] % [7.0, 5.0]) + 0.5 + rng.uniform(-0.1, 0.1, (g, 2))
+    bounds = np.stack([rng.uniform(0.25, 0.6, g), rng.uniform(0.2, 0.5, g), rng.uniform(0.2, 0.5, g)], 1)
+    yaw = rng.uniform(-np.pi, np.pi, g)
+    yaw[0] = 0.0
+    sem = rng.choice(ARKIT_IDS[:5], g)
+    sem[g - 1] = 24                                   # a class with ground truth and no prediction
+    rot = np.zeros((g, 9))
+    pts, owner = [], []
+    grid = np.zeros(g, bool)
+    grid[[0, 3]] = True                               # objects on a 1 cm grid: many collinear points on the hull
+    for i in range(g):
+        c, s = np.cos(yaw[i]), np.sin(yaw[i])
+        R = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+        rot[i] = R.T.reshape(-1)                      # the labels store the transpose (evaluation.py:261)
+        m = int(rng.integers(250, 600))
+        local = rng.uniform(-1.0, 1.0, (m, 3)) * bounds[i]
+        if grid[i]:
+            R = np.eye(3)
+            rot[i] = R.reshape(-1)
+            local = np.round(local, 2)
+        pts.append(local @ R.T + centers[i])
+        owner.append(np.full(m, i))
+    nb = 1500
+    pts.append(np.stack([rng.uniform(0, 8, nb), rng.uniform(0, 6, nb), rng.uniform(0, 2.4, nb)], 1))
+    owner.append(np.full(nb, -1))
+    pos = np.concatenate(pts).astype(np.float32)
+    owner = np.concatenate(owner)
+    perm = rng.permutation(len(pos))
+    pos, owner = pos[perm], owner[perm]
+    n = len(pos)
+    p64 = pos.astype(np.float64)
+    masks, labels, confs = [], [], []
+    for i in range(g - 1):
+        for rep in range(1 + (i % 4 == 1)):           # two predictions on one ground truth
+            own = owner == i
+            local = (p64 - centers[i])
+            cut = rng.choice([-2.0, -0.6, -0.2, 0.15])
+            axis = rng.normal(size=2); axis /= np.linalg.norm(axis)
+            m = own & (local[:, :2] @ axis > cut * bounds[i, 0])
+            near = (np.linalg.norm(local[:, :2], axis=1) < rng.choice([0.3, 0.8])) & (np.abs(local[:, 2]) < 0.4) & (owner == -1)
+            m |= near
+            masks.append(m); labels.append(sem[i]); confs.append(rng.random())
+    small = np.zeros(n, bool); small[np.nonzero(owner == 2)[0][:40]] = True           # under 50 points
+    masks.append(small); labels.append(sem[2]); confs.append(rng.random())
+    masks.append(owner == 4); labels.append(36)                                       # a class without any ground truth
+    confs.append(rng.random())
+    other = [c for c in ARKIT_IDS[:5] if c not in sem[[5]]][0]
+    masks.append(owner == 5); labels.append(other); confs.append(rng.random())        # right place, wrong class
+    masks.append((owner == -1) & (p64[:, 0] < 1.0) & (p64[:, 2] < 1.0)); labels.append(sem[0]); confs.append(rng.random())
+    labels_d = {'per_instance_bb_centers': centers.astype(np.float32), 'per_instance_bb_bounds': bounds.astype(np.float32),
+                'per_instance_bb_rotations': rot, 'per_instance_semantics': sem.astype(np.int64)}
+    pred = {'conf': np.array(confs, np.float32), 'label_id': np.array(labels, np.int32), 'mask': np.stack(masks)}
+    return pos, labels_d, pred
+
+
+def gen_detection():
+    """Oriented-box detection metric: ConvexHull hulls as evaluation.py:280-292 takes them, box3d_iou / calc_iou of every
+    same-class pair and the reference's own eval_det, from the imported utils.box_util / evaluate_detections / metric_util.
+    eval_det's np.array(BB) cannot hold hulls of different vertex counts on this numpy: it is handed (scene, index) handles of
+    equal shape and an IoU function that looks the real corner arrays up and calls the reference's get_iou_obb / get_iou."""
+    import contextlib
+    import io
+    _install_stubs()
+    pv = types.ModuleType('pyviz3d'); pv.visualizer = types.ModuleType('pyviz3d.visualizer')
+    sys.modules['pyviz3d'] = pv; sys.modules['pyviz3d.visualizer'] = pv.visualizer
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    from scipy.spatial import ConvexHull
+    import utils.box_util as B
+    import utils.evaluate_detections as E
+    rng = np.random.default_rng(11)
+    n_scenes = 4
+    out = {'n_scenes': np.array(n_scenes)}
+    real = {}                                          # (oriented, scene, 'p' / 'g', index) -> the reference's box
+    pred_all = {True: {}, False: {}}
+    gt_all = {True: {}, False: {}}
+    all_conf = {}
+    for si in range(n_scenes):
+        pos, labels, pred = detection_scene(rng, si)
+        p64 = pos.astype(np.float64)
+        name = 'room%d' % si
+        g = labels['per_instance_bb_centers'].shape[0]
+        for o in (True, False):
+            pred_all[o][name] = []; gt_all[o][name] = []
+        gcorners, gaabb = [], []
+        for i in range(g):                             # evaluation.py:257-270
+            bounds = labels['per_instance_bb_bounds'][i].astype(np.float64)
+            R = np.reshape(labels['per_instance_bb_rotations'][i], [3, 3]).T
+            c = labels['per_instance_bb_centers'][i].astype(np.float64)
+            gcorners.append(B.get_oriented_corners(bounds, R, c))
+            gaabb.append(np.concatenate([c, B.get_rotated_bounds(bounds, R) * 2.0], 0))
+            for o, box in ((True, gcorners[-1]), (False, gaabb[-1])):
+                real[(o, si, 'g', i)] = box
+                gt_all[o][name].append([labels['per_instance_semantics'][i], np.array([si, i])])
+        K = len(pred['conf'])
+        count = pred['mask'].sum(1)
+        hulls, off, box6 = [], [0], np.zeros((K, 6))
+        iou_o = np.zeros((K, g)); iou_a = np.zeros((K, g))
+        for r in range(K):                             # evaluation.py:272-299
+            positions = p64[pred['mask'][r]]
+            if positions.shape[0] < 50:
+                off.append(off[-1]); continue
+            p2 = positions[:, 0:2]
+            hv = p2[ConvexHull(p2).vertices]
+            zmin, zmax = np.min(positions[:, 2]), np.max(positions[:, 2])
+            prism = np.concatenate([np.concatenate([hv, np.ones([hv.shape[0], 1]) * zmin], 1),
+                                    np.concatenate([hv, np.ones([hv.shape[0], 1]) * zmax], 1)], 0)
+            pmin, pmax = np.min(positions, 0), np.max(positions, 0)
+            aabb = np.concatenate([(pmin + pmax) / 2.0, pmax - pmin], 0)
+            hulls.append(hv); off.append(off[-1] + len(hv)); box6[r] = np.concatenate([pmin, pmax])
+            for o, box in ((True, prism), (False, aabb)):
+                real[(o, si, 'p', r)] = box
+                pred_all[o][name].append([pred['label_id'][r], np.array([si, r]), pred['conf'][r]])
+            all_conf.setdefault(int(pred['label_id'][r]), []).append(pred['conf'][r])
+            for i in range(g):
+                if labels['per_instance_semantics'][i] != pred['label_id'][r]:
+                    continue
+                rect1 = [(prism[j, 0], prism[j, 1]) for j in range(prism.shape[0] // 2, -1, -1)]
+                rect2 = [(gcorners[i][j, 0], gcorners[i][j, 1]) for j in range(4)]
+                inter = B.polygon_clip(rect1, rect2)
+                assert inter is None or len(inter) >= 3, 'degenerate intersection polygon'
+                iou_o[r, i] = E.get_iou_obb(prism, gcorners[i])
+                iou_a[r, i] = E.get_iou(aabb, gaabb[i])
+        for t in (0.5, 0.25):
+            assert np.abs(iou_o - t).min() > 1e-6 and np.abs(iou_a - t).min() > 1e-6, 'an IoU within 1e-6 of a threshold'
+        out['s%d_pos' % si] = pos
+        out['s%d_mask' % si] = np.packbits(pred['mask'], axis=1)
+        out['s%d_n' % si] = np.array(len(pos))
+        out['s%d_conf' % si] = pred['conf']; out['s%d_label_id' % si] = pred['label_id']
+        for k, v in labels.items():
+            out['s%d_%s' % (si, k)] = v
+        out['s%d_count' % si] = count.astype(np.int64)
+        out['s%d_hull' % si] = np.concatenate(hulls, 0); out['s%d_hull_off' % si] = np.array(off, np.int64)
+        out['s%d_box6' % si] = box6
+        out['s%d_iou_obb' % si] = iou_o; out['s%d_iou_aabb' % si] = iou_a
+        out['s%d_hull_max' % si] = np.array(max(len(h) for h in hulls))
+    for c, v in all_conf.items():
+        assert len(set(float(x) for x in v)) == len(v), 'equal confidences in class %d' % c
+
+    def iou_of(o, fn):
+        def f(a, b):
+            return fn(real[(o, int(a[0]), 'p', int(a[1]))], real[(o, int(b[0]), 'g', int(b[1]))])
+        return f
+
+    for o, tag, fn in ((True, 'obb', E.get_iou_obb), (False, 'aabb', E.get_iou)):
+        for t in (0.5, 0.25):
+            with contextlib.redirect_stdout(io.StringIO()), np.errstate(all='ignore'):
+                rec, prec, ap = E.eval_det(pred_all[o], gt_all[o], ovthresh=t, get_iou_func=iou_of(o, fn))
+            key = '%s_%d' % (tag, round(t * 100))
+            cls = np.array([int(c) for c in ap.keys()], np.int64)
+            out[key + '_classes'] = cls
+            out[key + '_ap'] = np.array([ap[c] for c in ap.keys()], np.float64)
+            for c in ap.keys():
+                out['%s_rec_%d' % (key, int(c))] = np.asarray(rec[c], np.float64)
+                out['%s_prec_%d' % (key, int(c))] = np.asarray(prec[c], np.float64)
+            vals = [v for v in ap.values() if not np.isnan(v)]
+            out[key + '_map'] = np.array(np.mean(np.array(vals)))
+            print('eval_detection %s: mAP %.4f over %d classes (%s)' % (key, out[key + '_map'], len(vals),
+                                                                       ' '.join('%d:%.3f' % (int(c), ap[c]) for c in ap)))
+    _savez_fixed(os.path.join(OUT, 'eval_detection.npz'), out)
+    print('eval_detection.npz: %d bytes, largest hull %d vertices'
+          % (os.path.getsize(os.path.join(OUT, 'eval_detection.npz')), max(int(out['s%d_hull_max' % s]) for s in range(n_scenes))))
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
-    which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval']
+    which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval', 'detection']
     if 'iou_nms' in which:
         gen_iou_nms()
     if 'detection2mask' in which:
@@ -640,3 +823,5 @@ if __name__ == '__main__':
         gen_prepare2()
     if 'eval' in which:
         gen_eval()
+    if 'detection' in which:
+        gen_detection()

@@ -1,9 +1,10 @@
 """End-to-end run of everything the repository builds, on synthetic scenes: raw points + weak box labels -> device
 batch (prepare.voxelize_scene / box_supervision / collate) -> training steps as models/training.py:63-70 does them
 -> a checkpoint in the reference's format -> predictions -> instance masks -> ScanNet AP against the scenes' own
-instances (eval_metric.compute_eval).
+instances (eval_metric.compute_eval).  With --metric arkit the furniture instances are scored as oriented boxes as well
+(their labels' boxes, a yaw of zero): the ARKitScenes detection mAP of eval_detection.arkitscenes_eval after the last step.
 
-    python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 [--half 1]
+    python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 [--half 1] [--metric arkit]
 """
 import argparse
 import os
@@ -18,7 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from box2mask_amd import eval_metric, prepare, synth          # noqa: E402
+from box2mask_amd import eval_detection, eval_metric, prepare, synth          # noqa: E402
 from box2mask_amd.config import scannet_config                # noqa: E402
 from box2mask_amd.model import Model                          # noqa: E402
 
@@ -54,6 +55,25 @@ def evaluate(model, batch, raws):
     return avg
 
 
+def box_labels(raw):
+    """The furniture instances of a synthetic room as ARKitScenes labels: oriented boxes with the identity rotation."""
+    lab = raw['labels']
+    sem = lab['per_instance_semantics']
+    sel = np.nonzero((sem > 2) & (sem != 22))[0]
+    return {'per_instance_bb_centers': lab['per_instance_bb_centers'][sel], 'per_instance_bb_bounds': lab['per_instance_bb_bounds'][sel],
+            'per_instance_bb_rotations': np.tile(np.eye(3).reshape(1, 9), (len(sel), 1)), 'per_instance_semantics': sem[sel]}
+
+
+def evaluate_detection(model, batch, raws):
+    model.eval()
+    pred = model.get_prediction(batch, with_grad=False, to_cpu=True, min_size=True)
+    res = model.pred2mask(batch, pred, 'eval')
+    res = {r['name']: res[r['name']] for r in raws}
+    m, ap = eval_detection.arkitscenes_eval(res, raws, [box_labels(r) for r in raws], oriented_boxes=True, iou_t=0.5, verbose=False)
+    model.train()
+    return m, ap
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--scenes', type=int, default=4)
@@ -63,6 +83,8 @@ def main(argv=None):
     ap.add_argument('--eval-every', type=int, default=50)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--half', type=int, default=0, help='1: cfg.half_training (half activations / gradients in the trunk, half_train.py)')
+    ap.add_argument('--metric', choices=['scannet', 'arkit'], default='scannet',
+                    help='arkit: the oriented-box detection mAP (eval_detection.py) beside the ScanNet AP')
     args = ap.parse_args(argv)
     torch.manual_seed(args.seed)
     cfg = scannet_config(lr=args.lr, mlp_bb_scores_start_epoch=0, half_training=bool(args.half))       # score head trained from the first step
@@ -97,6 +119,10 @@ def main(argv=None):
     a1, a2 = evaluate(model, batch, raws), evaluate(fresh, batch, raws)
     assert a1['all_ap_50%'] == a2['all_ap_50%'], 'a reloaded checkpoint must predict the same masks'
     print('checkpoint %s reloaded: AP50 %.3f' % (loaded, a2['all_ap_50%']))
+    if args.metric == 'arkit':
+        m, by_class = evaluate_detection(fresh, batch, raws)
+        print('detection mAP@0.5 (oriented boxes) %.3f  over %d classes: %s'
+              % (m, len(by_class), '  '.join('%d:%.3f' % (c, v) for c, v in sorted(by_class.items()))))
     return history, a2
 
 
