@@ -634,6 +634,38 @@ int b2m_hull_box_iou(const double* hull, const int32_t* n_hull, const double* bo
 int b2m_aabb_iou(const double* box6, const int32_t* pcls, int32_t k, const double* gcenters, const double* boxes,
                  const int32_t* gcls, int32_t g, double* iou, void* stream);
 
+/* ---------------------------------------------------------------- S3DIS evaluation (wall clustering, instance merge, mPrec / mRec)
+ * The device half of Evaluater.s3dis_eval (models/evaluation.py:124-241) and utils/s3dis_util.py: the DBSCAN of
+ * clustering_for_background (:146-177), the greedy merge of the proposals (evaluation.py:177-193) and the count tables the
+ * instance pruning (:200-210) and s3dis_eval (s3dis_util.py:179-338) are made of.  The metric over those tables is host code
+ * (box2mask_amd/eval_s3dis.py). */
+
+/* DBSCAN with the labelling of sklearn.cluster.DBSCAN(eps, min_samples).fit(x).labels_, label for label.  x: fp64 (n, d) row-major,
+ * 3 <= d <= 8, finite values.  Rows a, b are neighbours when sum_j (a_j - b_j)^2 <= eps * eps (j ascending, fp64; a row neighbours
+ * itself); a row with >= min_samples neighbours is core; clusters are the connected components of the core rows, numbered in
+ * ascending order of their smallest core row; any other row takes the lowest cluster number among its core neighbours, or -1.
+ * labels[n] int32; *n_clusters (device int32) = number of clusters.  workspace: b2m_dbscan_workspace(n) bytes (-1: n out of range).
+ * n == 0: returns at once, nothing is launched or written (sklearn raises there).  Integer operations and fp64 comparisons only:
+ * every run gives the same labels. */
+int64_t b2m_dbscan_workspace(int64_t n);
+int b2m_dbscan(const double* x, int64_t n, int32_t d, double eps, int32_t min_samples, void* workspace, int32_t* labels,
+               int32_t* n_clusters, void* stream);
+
+/* Greedy merge of k proposals given as bit rows (bits[k][words], the layout of b2m_mask_pack, words = ceil(n / 64)) in row order:
+ * with o = |row| and f = |row & unlabeled|, row r is accepted when sem[r] >= sem_min, not ((double)f / (double)o < ratio) and
+ * not (f < min_points) (evaluation.py:181-191 with 3, 0.6, 200); an accepted row writes inst[p] = r + 1 and (sem_out != NULL)
+ * sem_out[p] = sem[r] at its still unlabeled points and clears them from `unlabeled`.  The call itself starts from inst = -1
+ * and every point unlabeled; sem_out is in / out (the caller fills it with the per-point semantics).  accepted[k]: 0 / 1.
+ * One launch of one workgroup: the rows are sequential by definition. */
+int b2m_paint_proposals(const uint64_t* bits, int64_t words, int32_t k, const int32_t* sem, int64_t n, int32_t sem_min,
+                        double ratio, int32_t min_points, uint64_t* unlabeled, int32_t* inst, int32_t* sem_out,
+                        int32_t* accepted, void* stream);
+
+/* hist[a[p] * nb + b[p]] += 1 over p < n (hist is zeroed by the call); points with a[p] outside [0, na) or b[p] outside [0, nb)
+ * are skipped; b == NULL stands for a column of zeros (a plain bincount with nb = 1).  na * nb <= B2M_JOINT_HIST_MAX. */
+#define B2M_JOINT_HIST_MAX (1 << 24)
+int b2m_joint_hist(const int32_t* a, const int32_t* b, int64_t n, int32_t na, int32_t nb, int32_t* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

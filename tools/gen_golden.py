@@ -805,10 +805,251 @@ def gen_detection():
           % (os.path.getsize(os.path.join(OUT, 'eval_detection.npz')), max(int(out['s%d_hull_max' % s]) for s in range(n_scenes))))
 
 
+S3DIS_GRID = 1.0 / 128.0
+S3DIS_NORMALS = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float64)
+
+
+def s3dis_room(rng, ri):
+    """One synthetic S3DIS-shaped room on an integer grid of 1/128 m with axis normals: ceiling, floor, two large walls, a wall of
+    fewer than 3000 points, furniture of classes 3 .. 12 (room 2 has no class 12), predicted semantics with a few wrong points
+    (some of them stray `wall` points) and proposals that the merge accepts or rejects by each of its three tests."""
+    L, W, H = 640, 512, 333
+    parts = []                                        # (grid (m, 3), normal index (m), class, instance)
+
+    def plane(m, axis, value, lo, hi, normal, cls, inst):
+        g = np.stack([rng.integers(lo[j], hi[j] + 1, m) for j in range(3)], 1)
+        g[:, axis] = value
+        parts.append((g, np.full(m, normal), cls, inst))
+
+    plane(5000, 2, H, (0, 0, 0), (L, W, 0), 5, 0, 0)
+    plane(5000, 2, 0, (0, 0, 0), (L, W, 0), 4, 1, 1)
+    plane(3600, 1, 0, (0, 0, 0), (L, 0, H), 2, 2, 2)
+    plane(3400, 0, 0, (0, 0, 0), (0, W, H), 0, 2, 3)
+    plane(2200, 1, W, (0, 0, 0), (L, 0, H), 3, 2, 4)
+    classes = list(range(3, 13)) + [5] if ri < 2 else list(range(3, 12)) + [5]
+    boxes = []
+    for i, cls in enumerate(classes):
+        cx, cy = 90 + (i % 4) * 150, 90 + (i // 4) * 150
+        sx, sy, sz = (int(v) for v in rng.integers(35, 60, 3))
+        m = int(rng.integers(700, 1000))
+        g = np.stack([rng.integers(cx - sx, cx + sx + 1, m), rng.integers(cy - sy, cy + sy + 1, m), rng.integers(1, 2 * sz, m)], 1)
+        parts.append((g, rng.integers(0, 6, m), cls, 5 + i))
+        boxes.append((cx, cy, sx, sy))
+    grid = np.concatenate([q[0] for q in parts]).astype(np.int16)
+    normal = np.concatenate([q[1] for q in parts]).astype(np.int8)
+    gt_sem = np.concatenate([np.full(len(q[0]), q[2]) for q in parts]).astype(np.int64)
+    gt_ins = np.concatenate([np.full(len(q[0]), q[3]) for q in parts]).astype(np.int64)
+    n = len(grid)
+    perm = rng.permutation(n)
+    grid, normal, gt_sem, gt_ins = grid[perm], normal[perm], gt_sem[perm], gt_ins[perm]
+    pred = gt_sem.copy()
+    obj = np.nonzero(gt_sem >= 3)[0]
+    wrong = rng.choice(obj, len(obj) // 100, replace=False)
+    pred[wrong] = rng.choice(sorted(set(classes)), len(wrong))
+    pred[rng.choice(obj, 60, replace=False)] = 2                                   # stray wall points
+    wall_a = np.nonzero(gt_ins == 2)[0]
+    pred[rng.choice(wall_a, 150, replace=False)] = 0                               # a few wall points taken for ceiling
+    masks = []
+
+    def subset(idx, keep):
+        m = np.zeros(n, bool)
+        m[rng.choice(idx, int(len(idx) * keep), replace=False)] = True
+        return m
+
+    def of(i):
+        return np.nonzero(gt_ins == 5 + i)[0]
+
+    floor = np.nonzero(gt_ins == 1)[0]
+    masks.append(subset(of(0), 0.9))                                               # accepted
+    masks.append(subset(of(0), 0.85))                                              # rejected: under 0.6 of it is still unlabeled
+    cx, cy, sx, sy = boxes[1]
+    near = floor[np.argsort(np.abs(grid[floor, 0] - cx) + np.abs(grid[floor, 1] - cy), kind='stable')[:150]]
+    m = subset(of(1), 0.9); m[near] = True
+    masks.append(m)                                                                # accepted, repaints 150 floor points
+    masks.append(subset(floor, 0.12))                                              # rejected: semantic class below 3
+    m = np.zeros(n, bool); m[of(2)[:150]] = True
+    masks.append(m)                                                                # rejected: fewer than 200 points
+    masks.append(subset(of(2), 0.9))
+    keeps = [0.95, 0.55, 0.4, 0.9, 0.8, 0.9, 0.9, 0.9]
+    for i in range(3, len(classes) - 1):                                           # the last object gets no proposal
+        masks.append(subset(of(i), keeps[(i - 3) % len(keeps)]))
+    masks.append(subset(np.nonzero(gt_ins == 3)[0], 0.3))                          # a wall: class 2, rejected
+    return grid, normal, gt_sem, gt_ins, pred, np.stack(masks)
+
+
+def s3dis_dbscan_case(seed, eps=0.2, min_samples=5, sig=0.09, sep=2.5, ncl=80, per=25, n=6000):
+    """6000 rows in 6-D (float32 values): Gaussian blobs in touching pairs, in uniform noise."""
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(0, 2.0, (ncl, 6))
+    u = rng.normal(size=(ncl // 2, 6))
+    c[1::2] = c[0::2] + u / np.linalg.norm(u, axis=1, keepdims=True) * sep * eps
+    pts = [c[i] + rng.normal(0, sig, (per, 6)) for i in range(ncl)]
+    pts.append(rng.uniform(-0.2, 2.2, (n - ncl * per, 6)))
+    x = np.concatenate(pts).astype(np.float32)
+    return x[rng.permutation(len(x))], eps, min_samples
+
+
+def gen_s3dis():
+    """S3DIS evaluation: tests/golden/eval_s3dis.npz from the reference's own code, imported unmodified -- utils/s3dis_util.py
+    (clustering_for_background, assign_semantics_to_proposals, s3dis_eval; sklearn's DBSCAN inside) and Evaluater.s3dis_eval
+    (models/evaluation.py:124-241), which is DRIVEN here for the merge stage: a fake model hands it the fixture's per-voxel logits
+    and masks, a list is the loader, s3dis.get_scene_names is a stub and s3dis_util's three functions are wrapped to record what
+    goes through them.  pyviz3d, quaternion, natsort and tensorboard get empty stand-ins where missing; np.float (gone from numpy)
+    is restored in this process only.  The fixture holds data only: positions as int16 steps of 1/128 m, normals as indices into
+    the six axis directions, masks bit-packed."""
+    import contextlib
+    import io
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from _s3dis_rule import dbscan_rule, margin
+    D = _dataloader_module()
+    for name in ('pyviz3d', 'pyviz3d.visualizer', 'quaternion', 'natsort', 'tensorboard', 'torch.utils.tensorboard'):
+        try:
+            __import__(name)
+        except Exception:
+            sys.modules[name] = types.ModuleType(name)
+    sys.modules['pyviz3d'].visualizer = sys.modules['pyviz3d.visualizer']
+    if not hasattr(sys.modules['torch.utils.tensorboard'], 'SummaryWriter'):
+        sys.modules['torch.utils.tensorboard'].SummaryWriter = object
+    if not hasattr(np, 'float'):
+        np.float = float
+    for n in ('scannet', 'arkitscenes', 's3dis'):
+        m = sys.modules['dataprocessing.' + n]
+        for attr in ('SCANNET', 'ARKITSCENES', 'S3DIS'):
+            for tail in ('_SEMANTIC_VALID_CLASS_IDS', '_SEMANTIC_ID2IDX', '_INSTANCE_ID2IDX'):
+                if not hasattr(m, attr + tail):
+                    setattr(m, attr + tail, None)
+    s3 = sys.modules['dataprocessing.s3dis']
+    s3.get_scene_names = lambda mode, cfg: []
+    s3.ID2NAME = ['class%d' % c for c in range(13)]
+    import models.evaluation as EV
+    import utils.s3dis_util as SU
+    from sklearn.cluster import DBSCAN
+
+    out = {}
+    # ---- DBSCAN-only cases
+    seed = 100
+    for ci in range(2):
+        while True:
+            seed += 1
+            x, eps, ms = s3dis_dbscan_case(seed)
+            x64 = x.astype(np.float64)
+            fit = DBSCAN(eps=eps, min_samples=ms).fit(x64)
+            lab = fit.labels_
+            core = np.zeros(len(x), bool); core[fit.core_sample_indices_] = True
+            rule, rcore, two = dbscan_rule(x64, eps, ms)
+            assert np.array_equal(rule, lab) and np.array_equal(rcore, core), 'the labelling rule does not reproduce sklearn'
+            ok = lab.max() + 1 >= 50 and ((lab >= 0) & ~core).sum() >= 500 and (lab < 0).sum() >= 1000 and two.sum() >= 20 and \
+                margin(x64, eps) >= 1e-12
+            if ok:
+                break
+        perm = np.random.default_rng(seed + 1000).permutation(len(x))
+        lab_p = DBSCAN(eps=eps, min_samples=ms).fit(x64[perm]).labels_
+        out['db%d_x' % ci] = x
+        out['db%d_eps' % ci] = np.float64(eps); out['db%d_min_samples' % ci] = np.int64(ms)
+        out['db%d_labels' % ci] = lab.astype(np.int16); out['db%d_core' % ci] = np.packbits(core)
+        out['db%d_perm' % ci] = perm.astype(np.int16); out['db%d_labels_perm' % ci] = lab_p.astype(np.int16)
+        print('eval_s3dis db%d: seed %d, %d clusters, %d border (%d between two clusters), %d noise, margin %.2e'
+              % (ci, seed, lab.max() + 1, ((lab >= 0) & ~core).sum(), two.sum(), (lab < 0).sum(), margin(x64, eps)))
+
+    # ---- rooms through Evaluater.s3dis_eval
+    rng = np.random.default_rng(2024)
+    rooms = [s3dis_room(rng, ri) for ri in range(3)]
+    batches, by_name = [], {}
+    for ri, (grid, normal, gt_sem, gt_ins, pred, masks) in enumerate(rooms):
+        name = 'room%d' % ri
+        scene = {'name': name, 'positions': grid.astype(np.float64) * S3DIS_GRID, 'normals': S3DIS_NORMALS[normal]}
+        labels = {'semantics': gt_sem, 'instances': gt_ins}
+        n = len(grid)
+        batches.append({'scene': [scene], 'labels': [labels], 'vox2point': [np.arange(n)]})
+        by_name[name] = (pred, masks)
+
+    class FakeModel:
+        def get_prediction(self, batch, with_grad=False, to_cpu=True, min_size=True):
+            pred, _ = by_name[batch['scene'][0]['name']]
+            return {'mlp_per_vox_semantics': torch.from_numpy(np.eye(13, dtype=np.float32)[pred])}
+
+        def pred2mask(self, batch, prediction, mode='eval'):
+            name = batch['scene'][0]['name']
+            return {name: {'mask': by_name[name][1].astype(np.uint8)}}
+
+    seen = {'background': [], 'proposal_semantics': [], 'wall_features': []}
+    real_bg, real_assign, real_eval = SU.clustering_for_background, SU.assign_semantics_to_proposals, SU.s3dis_eval
+
+    def bg(pred_semantics, coords, normals):
+        r = real_bg(pred_semantics, coords, normals)
+        seen['background'].append(r.copy())
+        w = pred_semantics == 2
+        seen['wall_features'].append(np.concatenate([coords[w], normals[w] * 2], 1))
+        return r
+
+    def assign(pred_semantics, masks):
+        r = real_assign(pred_semantics, masks)
+        seen['proposal_semantics'].append(np.array(r))
+        return r
+
+    def ev(pred_labels, gt_labels):
+        seen['pred_labels'], seen['gt_labels'] = pred_labels, gt_labels
+        with np.errstate(all='ignore'):
+            return real_eval(pred_labels, gt_labels)
+
+    SU.clustering_for_background, SU.assign_semantics_to_proposals, SU.s3dis_eval = bg, assign, ev
+    evaluater = object.__new__(EV.Evaluater)
+    evaluater.model = FakeModel()
+    evaluater.cfg = SimpleNamespace(eval_ths=[0.5, 0.03, 0.3, 0.6], s3dis_split_fold=5, full_resolution=False)
+    loader = SimpleNamespace(get_loader=lambda **kw: batches)
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            evaluater.s3dis_eval(loader)
+    finally:
+        SU.clustering_for_background, SU.assign_semantics_to_proposals, SU.s3dis_eval = real_bg, real_assign, real_eval
+    out['n_rooms'] = np.array(3)
+    for ri, (grid, normal, gt_sem, gt_ins, pred, masks) in enumerate(rooms):
+        fin = seen['pred_labels'][ri]
+        bgr = seen['background'][ri]
+        f = seen['wall_features'][ri]
+        assert margin(f, 0.35) >= 1e-12, 'a wall pair within 1e-12 of eps'
+        rule, _, _ = dbscan_rule(f, 0.35, 10)
+        assert np.array_equal(rule, DBSCAN(eps=0.35, min_samples=10).fit(f).labels_)
+        walls = np.unique(bgr[bgr >= 3])
+        sizes = np.bincount(rule[rule >= 0])
+        assert len(walls) == 2 and (sizes >= 3000).sum() == 2 and ((sizes < 3000) & (sizes > 1000)).sum() == 1 and (rule < 0).sum() >= 10, \
+            (walls, sizes, (rule < 0).sum())
+        # the merge: each rejection test decides at least once
+        ps = seen['proposal_semantics'][ri]
+        acc = np.array([(fin['instances'] == k + 1).any() for k in range(len(masks))])
+        assert ps[3] < 3 and ps[-1] < 3 and not acc[1] and ps[1] >= 3 and not acc[4] and ps[4] >= 3 and acc[0] and acc[2] and acc[5]
+        # the floor points proposal 2 repainted: background instance, a furniture class, under 200 -> removed
+        repainted = (bgr == 2) & (fin['semantics'] != 1)
+        assert 100 <= repainted.sum() < 200 and (fin['instances'][repainted] == -1).all()
+        for lab in (gt_sem, fin['semantics']):
+            assert set(np.unique(lab)) == (set(range(13)) if ri < 2 else set(range(12)))
+        out['r%d_n' % ri] = np.array(len(grid))
+        out['r%d_grid' % ri] = grid; out['r%d_normal' % ri] = normal
+        out['r%d_gt_semantics' % ri] = gt_sem.astype(np.int8); out['r%d_gt_instances' % ri] = gt_ins.astype(np.int16)
+        out['r%d_pred_semantics' % ri] = pred.astype(np.int8)
+        out['r%d_masks' % ri] = np.packbits(masks, axis=1)
+        out['r%d_background' % ri] = bgr.astype(np.int16)
+        out['r%d_proposal_semantics' % ri] = ps.astype(np.int8)
+        out['r%d_final_semantics' % ri] = np.asarray(fin['semantics']).astype(np.int8)
+        out['r%d_final_instances' % ri] = np.asarray(fin['instances']).astype(np.int16)
+    with contextlib.redirect_stdout(io.StringIO()), np.errstate(all='ignore'):
+        both = real_eval(seen['pred_labels'][:2], seen['gt_labels'][:2])
+        alone = real_eval(seen['pred_labels'][2:], seen['gt_labels'][2:])
+    assert np.isfinite(both[0]) and np.isfinite(both[1]) and np.isnan(alone[2][12]) and np.isnan(alone[3][12])
+    assert 0 < both[0] < 1 and 0 < both[1] < 1
+    for tag, r in (('rooms01', both), ('room2', alone)):
+        out[tag + '_mprec'] = np.float64(r[0]); out[tag + '_mrec'] = np.float64(r[1])
+        out[tag + '_precision'] = np.asarray(r[2], np.float64); out[tag + '_recall'] = np.asarray(r[3], np.float64)
+    path = os.path.join(OUT, 'eval_s3dis.npz')
+    _savez_fixed(path, out)
+    assert os.path.getsize(path) <= 1000000, os.path.getsize(path)
+    print('eval_s3dis.npz: %d bytes; rooms 0-1 mPrec %.4f mRec %.4f; room 2 alone mPrec %s' % (os.path.getsize(path), both[0], both[1], alone[0]))
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
-    which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval', 'detection']
+    which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval', 'detection', 's3dis']
     if 'iou_nms' in which:
         gen_iou_nms()
     if 'detection2mask' in which:
@@ -825,3 +1066,5 @@ if __name__ == '__main__':
         gen_eval()
     if 'detection' in which:
         gen_detection()
+    if 's3dis' in which:
+        gen_s3dis()
