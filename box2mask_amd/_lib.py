@@ -114,6 +114,15 @@ PROTOTYPES = {
     'b2m_obb_membership': [P, I64, P, P, P, I32, P, P, P],
     'b2m_seg_rank': [P, I64, P, P, I64, P, P],
     'b2m_seg_mode': [P, P, I64, I64, I32, P, P, P],
+    # ... augmentation and label recomputation (box2mask_amd/augment.py)
+    'b2m_aug_stats': [P, I64, P, P, P],
+    'b2m_aug_affine': [P, P, I64, P, P, P, P, I32, P],
+    'b2m_aug_axpy': [P, P, F64, I64, P],
+    'b2m_aug_blur': [P, P, I32, I32, I32, P],
+    'b2m_aug_displace': [P, I64, P, I32, I32, I32, P, P, P, F64, P],
+    'b2m_aug_vertex_normals': [P, I64, P, I64, P, P, P, P],
+    'b2m_aug_colour': [P, I64, P, I32, F64, P, P, P],
+    'b2m_inst_boxes': [P, P, P, I64, I64, P, P, P, P, P, P, P, P, P, P],
 }
 PLAIN = {'b2m_last_error': (C.c_char_p, []), 'b2m_version': (C.c_int, []), 'b2m_device_ok': (C.c_int, []),
          'b2m_reload_env': (C.c_int, []),

@@ -26,6 +26,13 @@ def scannet_config(**overrides):
         half_inference=False,        # build extension (no reference field): inference on half activations, see model.Model
         half_training=False,         # build extension: training passes with the trunk's activations / gradients in half (half_train.py)
         half_loss_scale=1024.0,      # ... and the factor its gradients are scaled by inside the half region (a power of two)
+        # augmentation (config_loader.py:189-227, read by augment.draw_params; everything off by default as in the reference --
+        # configs/scannet.txt switches on augmentation, rotation_90_aug, flipping_aug 0.5, scaling_aug [1, .8, 1.2] and apply_hue_aug,
+        # the last of which augment.py refuses)
+        augmentation=False, rotation_aug=[0.0, 3.141592653589793 / 100, 1], rotation_90_aug=False, flipping_aug=0.0,
+        HAIS_jitter_aug=False, elastic_distortion=0.0, elastic_distortion_HAIS=0.0, position_jittering=[0.0, 0.01],
+        scaling_aug=[0.0, 0.9, 1.1], chromatic_auto_contrast=0.0, chromatic_translation=[0.0, 0.1],
+        color_jittering_aug=[0.0, 0.1], random_brightness=[0.0, 0.1], mix_3d_color_aug=False, apply_hue_aug=False,
     )
     for k, v in overrides.items():
         setattr(cfg, k, v)

@@ -106,6 +106,58 @@ int b2m_seg_rank(const int64_t* segments, int64_t n_pts, const uint64_t* tkeys, 
 int b2m_seg_mode(const int32_t* seg_of_point, const int32_t* cls, int64_t n_pts, int64_t n_seg, int32_t n_class,
                  int32_t* hist, int32_t* mode_cls, void* stream);
 
+/* ---- scene augmentation and label recomputation (box2mask_amd/augment.py): the stage the reference runs before the
+ * voxelisation -- read_scene's augmentation block (dataprocessing/scannet.py:161-247, dataprocessing/augmentation.py) and
+ * compute_bounding_box (:321-367).  fp64 arithmetic without contraction, no floating-point atomics: the same bits run to
+ * run.  Every entry checks its arguments on the host and returns B2M_ERR_ARG before any launch: zero points, a grid axis
+ * shorter than 2 nodes and NULL pointers are such arguments.  Pointers named *_host are read on the host during the call. ---- */
+
+/* stats[0:3] = column mean, [3:6] = column min, [6:9] = column max, [9:12] = column max of |x| of the (n,3) array x.
+ * Fixed-order sums (a function of n alone).  partial: double[256 * 12] scratch. */
+int b2m_aug_stats(const double* x, int64_t n, double* partial, double* stats, void* stream);
+
+/* pos[p] <- (pos[p] - c) M^T + (recentre ? c : 0) + t, with M row-major 3x3, c = c_dev (3 doubles on the device, e.g. the
+ * mean or the min of b2m_aug_stats) when given, else c_host, else the origin; t_host may be NULL (zero).
+ * normals (may be NULL) <- normalised cof(M) n, cof(M) the cofactor matrix: what recomputing area-weighted vertex normals
+ * on the transformed mesh gives, sign flip under mirroring included.  A zero vector becomes (0,0,1). */
+int b2m_aug_affine(double* pos, double* normals, int64_t n, const double* m_host, const double* c_host,
+                   const double* c_dev, const double* t_host, int32_t recentre, void* stream);
+
+/* x[i] <- x[i] + a * y[i] for n elements (position jitter, scannet.py:202-204). */
+int b2m_aug_axpy(double* x, const double* y, double a, int64_t n, void* stream);
+
+/* Six zero-padded 3-tap passes (x,y,z,x,y,z) over the fp32 grid (nx,ny,nz,3), weight float32(1)/float32(3), fp64 sums
+ * rounded to fp32 after every pass: augmentation.py:74-87 and :172-183 (scipy.ndimage.convolve, mode='constant').
+ * tmp: a second buffer of the grid's size; the result is in `grid`. */
+int b2m_aug_blur(float* grid, float* tmp, int32_t nx, int32_t ny, int32_t nz, void* stream);
+
+/* pos[p] += magnitude * trilinear(grid, pos[p]): RegularGridInterpolator(ax, grid, bounds_error=0, fill_value=0) with
+ * ax[a] = np.linspace(lo[a], hi[a], n[a]) (nodes lo + i*step, the last one exactly hi).  A point outside any axis is not
+ * moved; a point on the last node is inside.  grid: fp32 (nx,ny,nz,3) on the device. */
+int b2m_aug_displace(double* pos, int64_t n, const float* grid, int32_t nx, int32_t ny, int32_t nz, const double* lo_host,
+                     const double* step_host, const double* hi_host, double magnitude, void* stream);
+
+/* normals[v] = normalised sum over the faces f of vertex v, in ascending f, of (p1 - p0) x (p2 - p0); a zero sum becomes
+ * (0,0,1).  faces: (n_faces,3) vertex indices; row_ptr[n_vert + 1], face_of[3 * n_faces]: the vertex-to-face CSR. */
+int b2m_aug_vertex_normals(const double* pos, int64_t n_vert, const int64_t* faces, int64_t n_faces, const int64_t* row_ptr,
+                           const int64_t* face_of, double* normals, void* stream);
+
+/* One fused pass over the (n,3) colours in the reference's order; flags: 1 = ChromaticAutoContrast with `blend`
+ * (augmentation.py:134-146; stats = b2m_aug_stats of the colours; a constant channel gives NaN as numpy does), 2 =
+ * ChromaticTranslation by the row tr_host, clipped to [0,1] (:108-112), 4 = color_jittering by the device array
+ * jitter (n,3), clipped (:52-61). */
+int b2m_aug_colour(double* colors, int64_t n, const double* stats, int32_t flags, double blend, const double* tr_host,
+                   const double* jitter, void* stream);
+
+/* compute_bounding_box (scannet.py:321-367) for instance ids in [0, n_inst): per-instance fp64 min / max by 64-bit integer
+ * atomics (order independent), semantics of the lowest-index point, centre = (min + max) / 2, bounds = max - centre, cast to
+ * float32 where the reference stores them; a second pass for offsets = centre - point, their norms and the radius.
+ * *missing = number of ids in [0, n_inst) without a point (the ids are not dense).  acc: uint64[8 * n_inst] scratch,
+ * centers64: double[3 * n_inst] scratch / out; offsets (n,3), distances (n,) float32. */
+int b2m_inst_boxes(const double* pos, const int64_t* instances, const int64_t* semantics, int64_t n, int64_t n_inst,
+                   uint64_t* acc, double* centers64, int32_t* per_sem, float* per_centers, float* per_bounds,
+                   float* per_radius, float* offsets, float* distances, int32_t* missing, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

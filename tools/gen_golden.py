@@ -1046,10 +1046,160 @@ def gen_s3dis():
     print('eval_s3dis.npz: %d bytes; rooms 0-1 mPrec %.4f mRec %.4f; room 2 alone mPrec %s' % (os.path.getsize(path), both[0], both[1], alone[0]))
 
 
+def gen_augment():
+    """Augmentation and label recomputation: tests/golden/augment.npz from the reference's own elastic_distortion, HAIS_elastic,
+    ChromaticAutoContrast, ChromaticTranslation, color_jittering (dataprocessing/augmentation.py) and compute_bounding_box
+    (dataprocessing/scannet.py), imported unmodified through stand-ins for open3d, albumentations, pyviz3d and configargparse.
+    While they run, scipy.ndimage.filters.convolve and scipy.interpolate.RegularGridInterpolator are wrapped to record the drawn
+    noise, the blurred grid and the axes; the blend / translation / jitter operands are re-drawn from the recorded seeds.  The
+    one case the reference's functions cannot reach -- points outside the axes and on the last node -- goes through the same
+    RegularGridInterpolator call with the same arguments.  Data only; the same bytes on every run.  Every case records the
+    output of every step; the per-step outputs of the 5000-point case go to a second file, tests/golden/augment_steps.npz,
+    because no committed file may exceed 1 MiB (together the two stay far below the largest fixture)."""
+    import random
+    import scipy
+    import scipy.interpolate
+    import scipy.ndimage
+    import scipy.ndimage.filters
+    _install_stubs()
+    alb = types.ModuleType('albumentations')
+    alb.load = lambda *a, **k: None
+    for n in ('Normalize', 'Compose', 'HueSaturationValue', 'RandomBrightnessContrast'):
+        setattr(alb, n, lambda *a, **k: None)
+    sys.modules['albumentations'] = alb
+    for name in ('pyviz3d', 'pyviz3d.visualizer', 'configargparse'):
+        if name not in sys.modules:
+            sys.modules[name] = types.ModuleType(name)
+    sys.modules['pyviz3d'].visualizer = sys.modules['pyviz3d.visualizer']
+    for name in [k for k in sys.modules if k == 'dataprocessing' or k.startswith('dataprocessing.')]:
+        del sys.modules[name]                                   # the empty stand-ins of the prepare targets
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    import dataprocessing.augmentation as AUG
+    import dataprocessing.scannet as SC
+
+    calls, axes = [], []
+    steps_out = {}
+    real_convolve, real_rgi = scipy.ndimage.filters.convolve, scipy.interpolate.RegularGridInterpolator
+
+    def convolve(x, w, **kw):
+        y = real_convolve(x, w, **kw)
+        calls.append((np.array(x, copy=True), np.array(y, copy=True)))
+        return y
+
+    def rgi(ax, values, **kw):
+        axes.append([np.array(a, copy=True) for a in ax])
+        return real_rgi(ax, values, **kw)
+
+    scipy.ndimage.filters.convolve = convolve
+    scipy.interpolate.RegularGridInterpolator = rgi
+    out = {}
+    rng = np.random.default_rng(606)
+    metre = (AUG.SCANNET_ELASTIC_DISTORT_PARAMS, ((6.0, 40.0), (20.0, 160.0)))         # scannet.py:190, :196-197 at 2 cm voxels
+    # name, points, lower corner, extent, (elastic params, hais params)
+    cases = [('p1', 1, (0.3, 0.2, 0.1), (1, 1, 1), metre), ('p63', 63, (0, 0, 0), (1.1, 0.9, 0.5), metre),
+             ('p64', 64, (0, 0, 0), (1.1, 0.9, 0.5), metre), ('p65', 65, (0.5, 0.1, 0), (1.1, 0.9, 0.5), metre),
+             ('p1000', 1000, (0, 0, 0), (2.0, 1.5, 1.0), metre), ('p5000', 5000, (0.2, 0.1, 0), (3.0, 2.5, 1.5), metre),
+             ('flat', 300, (0, 0, 0.75), (1.5, 1.2, 0.0), metre),
+             # voxel units with negative coordinates: larger HAIS grids; elastic granularities to match
+             ('neg', 300, (-25, -20, -5), (60, 30, 10), (((4.0, 8.0), (16.0, 32.0)), ((6.0, 40.0), (20.0, 160.0))))]
+    out['case_names'] = np.array([c[0] for c in cases])
+    for ci, (name, P, lo, ext, (el, ha)) in enumerate(cases):
+        pos = np.asarray(lo, np.float64) + rng.random((P, 3)) * np.asarray(ext, np.float64)
+        dst = out if P <= 1000 else steps_out                                          # (file size: see the docstring)
+        out[name + '_pos'] = pos
+        out[name + '_el_params'] = np.asarray(el, np.float64)
+        out[name + '_ha_params'] = np.asarray(ha, np.float64)
+        cur = pos.copy()
+        for k, (gran, mag) in enumerate(el):                                           # scannet.py:189-192
+            del calls[:], axes[:]
+            np.random.seed(1000 + 10 * ci + k)
+            cur = AUG.elastic_distortion(cur, gran, mag)
+            assert len(calls) == 6 and len(axes) == 1
+            out['%s_el%d_noise' % (name, k)] = calls[0][0]
+            out['%s_el%d_blur' % (name, k)] = calls[5][1]
+            for a in range(3):
+                out['%s_el%d_ax%d' % (name, k, a)] = axes[0][a]
+            (out if k == 1 else dst)['%s_el%d_out' % (name, k)] = cur.copy()
+        cur = pos.copy()
+        for k, (gran, mag) in enumerate(ha):                                           # scannet.py:195-198
+            del calls[:], axes[:]
+            np.random.seed(2000 + 10 * ci + k)
+            cur = AUG.HAIS_elastic(cur, gran, mag)
+            assert len(calls) == 18 and len(axes) == 3
+            out['%s_ha%d_noise' % (name, k)] = np.stack([calls[c][0] for c in range(3)])
+            out['%s_ha%d_blur' % (name, k)] = np.stack([calls[15 + c][1] for c in range(3)])
+            for a in range(3):
+                out['%s_ha%d_ax%d' % (name, k, a)] = axes[0][a]
+            dst['%s_ha%d_out' % (name, k)] = cur.copy()
+        cur -= cur.min(0)
+        out[name + '_ha_final'] = cur.copy()
+    scipy.ndimage.filters.convolve = real_convolve
+    scipy.interpolate.RegularGridInterpolator = real_rgi
+    # ---- trilinear alone: points outside every axis in turn, on the first and on the last node, on interior nodes
+    dims = (4, 3, 5)
+    grid = rng.standard_normal(dims + (3,)).astype(np.float32)
+    lo, hi = np.array([-0.4, 0.1, 1.0]), np.array([0.8, 0.5, 3.0])
+    ax = [np.linspace(a, b, d) for a, b, d in zip(lo, hi, dims)]
+    pts = lo + rng.random((40, 3)) * (hi - lo)
+    pts[0] = hi; pts[1] = lo; pts[2] = [ax[0][1], ax[1][1], ax[2][3]]
+    pts[3] = [hi[0], 0.3, 2.0]; pts[4] = [0.0, hi[1], 2.0]; pts[5] = [0.0, 0.3, hi[2]]
+    pts[6] = [hi[0] + 1e-9, 0.3, 2.0]; pts[7] = [0.0, lo[1] - 1e-9, 2.0]; pts[8] = [0.0, 0.3, hi[2] + 0.5]
+    pts[9] = [-5.0, -5.0, -5.0]; pts[10] = [np.nextafter(hi[0], 9.0), 0.3, 2.0]; pts[11] = [np.nextafter(lo[0], -9.0), 0.3, 2.0]
+    interp = real_rgi(ax, grid, bounds_error=0, fill_value=0)
+    out['tri_grid'] = grid; out['tri_lo'] = lo; out['tri_hi'] = hi; out['tri_pts'] = pts; out['tri_mag'] = np.float64(1.6)
+    out['tri_out'] = pts + interp(pts) * 1.6
+    # ---- colour: the three transforms chained in read_scene's order; `const` has a constant channel (scale = inf, NaN)
+    for name, P, seed in (('col', 500, 31), ('colconst', 64, 32)):
+        col = rng.random((P, 3))
+        col[::7] = np.round(col[::7])                                               # exact 0 / 1 values among them
+        if name == 'colconst':
+            col[:, 1] = 0.25
+        out[name + '_in'] = col.copy()
+        random.seed(seed)
+        with np.errstate(all='ignore'):
+            c1 = AUG.ChromaticAutoContrast()(col.copy())
+        random.seed(seed); random.random()
+        out[name + '_blend'] = np.float64(random.random())
+        out[name + '_contrast'] = c1.copy()
+        random.seed(seed); np.random.seed(seed)
+        assert random.random() < 0.95
+        c2 = AUG.ChromaticTranslation(0.1)(c1.copy())
+        np.random.seed(seed)
+        out[name + '_tr'] = (np.random.rand(1, 3) - 0.5) * 1.0 * 2 * 0.1
+        out[name + '_translation'] = c2.copy()
+        np.random.seed(seed + 100)
+        c3 = AUG.color_jittering(c2.copy(), -0.1, 0.1)
+        np.random.seed(seed + 100)
+        out[name + '_jitter'] = np.random.uniform(-0.1, 0.1, c2.shape)
+        out[name + '_jittered'] = c3
+    # ---- instance boxes: nine instances, one of a single point
+    P, I = 1200, 9
+    inst = rng.integers(0, I - 1, P).astype(np.int32)
+    inst[777] = I - 1
+    sem_of = np.array([3, 5, 5, 1, 2, 7, 39, 24, 4], np.int32)
+    centre = rng.uniform(-2, 4, (I, 3))
+    pos = centre[inst] + rng.normal(0, 0.3, (P, 3)) * rng.uniform(0.3, 1.5, (I, 3))[inst]
+    sem = sem_of[inst]
+    names = ('bb_centers', 'bb_offsets', 'bb_bounds', 'bb_center_distances', 'bb_radius', 'unique_instances', 'per_instance_semantics',
+             'per_instance_bb_centers', 'per_instance_bb_bounds', 'per_instance_bb_radius')
+    out['box_pos'] = pos; out['box_instances'] = inst; out['box_semantics'] = sem
+    for n, v in zip(names, SC.compute_bounding_box(pos, inst, sem)):
+        out['box_' + n] = v
+    path = os.path.join(OUT, 'augment.npz')
+    _savez_fixed(path, out)
+    assert os.path.getsize(path) <= 1000000, os.path.getsize(path)
+    print('augment.npz: %d bytes, %d arrays' % (os.path.getsize(path), len(out)))
+    path2 = os.path.join(OUT, 'augment_steps.npz')
+    _savez_fixed(path2, steps_out)
+    assert os.path.getsize(path2) <= 1000000 and os.path.getsize(path) + os.path.getsize(path2) <= 3529354       # <= prepare.npz
+    print('augment_steps.npz: %d bytes, %s' % (os.path.getsize(path2), sorted(steps_out)))
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
-    which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval', 'detection', 's3dis']
+    which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval', 'detection', 's3dis', 'augment']
     if 'iou_nms' in which:
         gen_iou_nms()
     if 'detection2mask' in which:
@@ -1068,3 +1218,5 @@ if __name__ == '__main__':
         gen_detection()
     if 's3dis' in which:
         gen_s3dis()
+    if 'augment' in which:
+        gen_augment()

@@ -4,7 +4,11 @@ batch (prepare.voxelize_scene / box_supervision / collate) -> training steps as 
 instances (eval_metric.compute_eval).  With --metric arkit the furniture instances are scored as oriented boxes as well
 (their labels' boxes, a yaw of zero): the ARKitScenes detection mAP of eval_detection.arkitscenes_eval after the last step.
 
-    python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 [--half 1] [--metric arkit]
+    python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 [--half 1] [--metric arkit] [--augment]
+
+--augment (off by default): every step trains on a batch whose scenes went through augment.augment_scenes with parameters drawn per
+scene per step from the values of configs/scannet.txt (rotation_90_aug, flipping_aug 0.5, scaling_aug 0.8 - 1.2) and whose box
+labels augment.instance_labels recomputed from the augmented positions; the evaluations stay on the un-augmented scenes.
 """
 import argparse
 import os
@@ -19,7 +23,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from box2mask_amd import eval_detection, eval_metric, prepare, synth          # noqa: E402
+from box2mask_amd import augment, eval_detection, eval_metric, prepare, synth          # noqa: E402
 from box2mask_amd.config import scannet_config                # noqa: E402
 from box2mask_amd.model import Model                          # noqa: E402
 
@@ -35,6 +39,19 @@ def build_batch(seeds, voxels, mode, cfg_sup):
             prepare.box_supervision(it, raw['labels'], cfg_sup)
         items.append(it); raws.append(raw)
     return prepare.collate(items, mode), raws
+
+
+def augmented_batch(raws, aug_cfg, rng, cfg_sup):
+    """One training batch of freshly augmented scenes: parameters per scene, labels from the augmented positions."""
+    outs = augment.augment_scenes(raws, [augment.draw_params(aug_cfg, generator=rng) for _ in raws])
+    items = prepare.voxelize_scenes(outs, 0.02)
+    for it, out, raw in zip(items, outs, raws):
+        lab = raw['labels']
+        inst = lab['seg2inst'][raw['segments']]
+        labels = augment.instance_labels(out, lab['per_instance_semantics'][inst], inst, lab['seg2inst'])
+        it['scene'] = {'name': raw['name']}
+        prepare.box_supervision(it, labels, cfg_sup)
+    return prepare.collate(items, 'train')
 
 
 def ground_truth_ids(raw):
@@ -85,12 +102,17 @@ def main(argv=None):
     ap.add_argument('--half', type=int, default=0, help='1: cfg.half_training (half activations / gradients in the trunk, half_train.py)')
     ap.add_argument('--metric', choices=['scannet', 'arkit'], default='scannet',
                     help='arkit: the oriented-box detection mAP (eval_detection.py) beside the ScanNet AP')
+    ap.add_argument('--augment', action='store_true',
+                    help='train on scenes augmented on the device, parameters drawn per scene per step (augment.py)')
     args = ap.parse_args(argv)
     torch.manual_seed(args.seed)
     cfg = scannet_config(lr=args.lr, mlp_bb_scores_start_epoch=0, half_training=bool(args.half))       # score head trained from the first step
     cfg.checkpoint_path = tempfile.mkdtemp(prefix='b2m_ckpt_') + '/'
     sup = SimpleNamespace(smallest_bb_heuristic=True)
     batch, raws = build_batch(range(args.scenes), args.voxels, 'train', sup)
+    if args.augment:
+        aug_cfg = scannet_config(augmentation=True, rotation_90_aug=True, flipping_aug=0.5, scaling_aug=[1.0, 0.8, 1.2])   # configs/scannet.txt:32-36
+        aug_rng = np.random.default_rng(args.seed)
     model = Model(cfg, *synth.scannet_tables())
     opt = torch.optim.Adam(model.parameters(), lr=cfg.lr, fused=True)
     model.train()
@@ -98,7 +120,7 @@ def main(argv=None):
     t0 = time.time()
     for step in range(args.steps):
         opt.zero_grad()
-        losses = model.compute_loss(batch, epoch=step)
+        losses = model.compute_loss(augmented_batch(raws, aug_cfg, aug_rng, sup) if args.augment else batch, epoch=step)
         losses['optimization_loss'].backward()
         opt.step()
         if step % 10 == 0 or step == args.steps - 1:
