@@ -150,7 +150,12 @@ __global__ void detection_loss_final_kernel(const double* __restrict__ o, double
         // rounding error below zero for (nearly) constant inputs: clamped before the root (a negative product gave NaN -> +-inf
         // through the floor below).  Zero variance -- all IoUs 0 at a fresh initialisation -- reads 0 here, as model._pearsonr
         // does; scipy.stats.pearsonr returns NaN with a warning for such input
-        const double va = ca > 0.0 ? ca : 0.0, vb = cb > 0.0 ? cb : 0.0;
+        // The uncentred form  sum x^2 - (sum x)^2 / F  equals the centred sum only up to the rounding of its two terms, each about
+        // (tree depth + blocks) * 2^-53 of sum x^2: for constant input (every score logit equal) it came out as +-1e-13 instead of
+        // the exact 0 of  sum (x - mean)^2, and a positive one turned the correlation into ~1e-8 of noise over noise.  A
+        // centred sum below that rounding is zero variance (tests/test_gpu_loss.py, case equal_scores)
+        const double noise = (double)((S + 255) / 256 + 16) * 0x1p-52;
+        const double va = ca > noise * o[5] ? ca : 0.0, vb = cb > noise * o[6] ? cb : 0.0;
         const double den = sqrt(va * vb);
         res[5] = den > 1e-300 ? (float)(cab / den) : 0.f;
     }
