@@ -123,6 +123,9 @@ PROTOTYPES = {
     'b2m_aug_vertex_normals': [P, I64, P, I64, P, P, P, P],
     'b2m_aug_colour': [P, I64, P, I32, F64, P, P, P],
     'b2m_inst_boxes': [P, P, P, I64, I64, P, P, P, P, P, P, P, P, P, P],
+    # ... nearest-neighbour index (box2mask_amd/neighbors.py)
+    'b2m_nn_build': [P, I64, P, P],
+    'b2m_nn_query': [P, I64, P, P, I64, P, P, P],
 }
 PLAIN = {'b2m_last_error': (C.c_char_p, []), 'b2m_version': (C.c_int, []), 'b2m_device_ok': (C.c_int, []),
          'b2m_reload_env': (C.c_int, []),
@@ -136,6 +139,7 @@ PLAIN = {'b2m_last_error': (C.c_char_p, []), 'b2m_version': (C.c_int, []), 'b2m_
          'b2m_rulebook_cnt_size': (C.c_int64, [I32, I64]),
          'b2m_radix_argsort_scratch': (C.c_int64, [I64]),
          'b2m_dbscan_workspace': (C.c_int64, [I64]),
+         'b2m_nn_workspace': (C.c_int64, [I64]),
          'b2m_xchg_size': (C.c_int64, []), 'b2m_xchg_max_doubles': (C.c_int32, []), 'b2m_xchg_max_ranks': (C.c_int32, []),
          'b2m_xchg_alloc': (C.c_int, [C.POINTER(C.c_void_p), P]), 'b2m_xchg_open': (C.c_int, [P, C.POINTER(C.c_void_p)]),
          'b2m_xchg_close': (C.c_int, [P]), 'b2m_xchg_free': (C.c_int, [P]),

@@ -7,8 +7,14 @@ room and one full-length boolean ``&`` / ``|`` per (prediction, ground truth) pa
 ``b2m_paint_proposals`` and ``b2m_joint_hist`` (include/b2m.h, csrc/cluster.hip); the metric over the resulting tables walks a few
 hundred records per room and stays on the host (``s3dis_eval_from_counts``).
 
+Full resolution (``cfg.full_resolution``, evaluation.py:151-154 and :213-222): the labels predicted on the sampled room are carried
+to every point of the unsampled room through ``sparse2dense`` -- the nearest sampled point, box2mask_amd.neighbors -- and scored
+against the full room's ground truth.  The caller hands the unsampled rooms to ``evaluate_rooms(..., full_rooms=...)``; the
+reference reads them through its dataset module.
+
 Deviations from the reference, both where it raises: ``dbscan`` of zero rows returns zero labels (sklearn raises), and an empty
-proposal mask gets semantic class 0 (``np.bincount([]).argmax()`` raises).
+proposal mask gets semantic class 0 (``np.bincount([]).argmax()`` raises).  Among sampled points at exactly the same distance
+``sparse2dense`` takes the lowest row.
 """
 from __future__ import annotations
 
@@ -275,19 +281,36 @@ def s3dis_eval(pred_labels, gt_labels, details=False):
     return s3dis_eval_from_counts([s3dis_counts(p, g) for p, g in zip(pred_labels, gt_labels)], details=details)
 
 
-def evaluate_rooms(model, batches, details=False, viz_path=None):
+def sparse2dense(full_positions, sampled_positions):
+    """For every point of the unsampled room the index of the nearest sampled point: int64 (n_full) on the device.
+
+    The reference CALLS ``get_sparse2dense(scene_full, scene, cfg)`` (evaluation.py:154) but defines it nowhere.  This is the
+    definition its uses at :219-220 require -- an index into the sampled room per point of the full one -- built on the search the
+    reference uses everywhere else (1-nearest neighbour, ball tree).  Lowest row among exactly equidistant sampled points."""
+    from .neighbors import NearestIndex
+    return NearestIndex(sampled_positions).query(full_positions)
+
+
+def evaluate_rooms(model, batches, details=False, viz_path=None, full_rooms=None):
     """The loop of Evaluater.s3dis_eval (evaluation.py:137-231) over batches of ONE room each: prediction, masks, per-point
-    semantics from the per-voxel head, ``room_labels``, then ``s3dis_eval`` against batch['labels'][0]['semantics' / 'instances']."""
+    semantics from the per-voxel head, ``room_labels``, then ``s3dis_eval`` against batch['labels'][0]['semantics' / 'instances'].
+
+    With ``cfg.full_resolution`` the unsampled rooms come through ``full_rooms``: a sequence aligned with ``batches`` of
+    ``(scene_full, labels_full)`` dicts ('positions'; 'semantics', 'instances'), or a callable ``name -> (scene_full, labels_full)``
+    (what ``s3dis.process_scene`` returns with ``point_sampling_rate = None``, evaluation.py:152-153).  The predicted semantics and
+    instances are gathered through ``sparse2dense`` and scored against the full room's ground truth (evaluation.py:213-222)."""
     cfg = model.cfg
-    if getattr(cfg, 'full_resolution', False):
-        raise NotImplementedError('evaluate_rooms: cfg.full_resolution (get_sparse2dense over the unsampled room) is not implemented')
+    full = bool(getattr(cfg, 'full_resolution', False))
+    if full and full_rooms is None:
+        raise NotImplementedError('evaluate_rooms: cfg.full_resolution needs the unsampled rooms: pass full_rooms= (a sequence aligned '
+                                  'with the batches of (scene_full, labels_full), or a callable name -> (scene_full, labels_full))')
     if viz_path is not None:
         raise NotImplementedError('evaluate_rooms: the visualisation path (visualize_prediction) is not implemented')
     if cfg.mlp_per_vox_semantics not in cfg.network_heads:
         raise ValueError('evaluate_rooms needs the per-voxel semantics head (%s)' % cfg.mlp_per_vox_semantics)
     dev = _dev()
     pred_labels, gt_labels = [], []
-    for batch in batches:
+    for i, batch in enumerate(batches):
         assert len(batch['scene']) == 1, 'S3DIS is evaluated with batch size 1 (evaluation.py:131)'
         prediction = model.get_prediction(batch, with_grad=False, to_cpu=True, min_size=True)
         scene, labels = batch['scene'][0], batch['labels'][0]
@@ -295,6 +318,11 @@ def evaluate_rooms(model, batches, details=False, viz_path=None):
         results = model.pred2mask(batch, prediction, 'eval')
         v2p = torch.as_tensor(np.asarray(batch['vox2point'][0])).long()
         sem = vox_sem.cpu()[v2p]
-        pred_labels.append(room_labels(sem.to(dev), scene['positions'], scene['normals'], results[scene['name']]['mask']))
+        pred = room_labels(sem.to(dev), scene['positions'], scene['normals'], results[scene['name']]['mask'])
+        if full:
+            scene_full, labels = full_rooms(scene['name']) if callable(full_rooms) else full_rooms[i]
+            s2d = sparse2dense(scene_full['positions'], scene['positions'])
+            pred = {'semantics': pred['semantics'][s2d], 'instances': pred['instances'][s2d]}
+        pred_labels.append(pred)
         gt_labels.append({'semantics': labels['semantics'], 'instances': labels['instances']})
     return s3dis_eval(pred_labels, gt_labels, details=details)

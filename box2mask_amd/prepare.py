@@ -435,3 +435,50 @@ def collate(items, mode: str = 'train') -> dict:
         if k in ret:
             ret[k] = torch.cat([torch.as_tensor(v).to(dev) for v in ret[k]], 0).to(dt)
     return ret
+
+
+def s3dis_point_labels(scene_pts, instance_clouds, class_ids):
+    """Label transfer of the raw S3DIS dataset: ``get_labels`` of /root/reference/dataprocessing/prepare_s3dis.py:76-121 on the device.
+
+    Every annotation cloud (``instance_clouds[k]``: (m_k, >= 3), the columns after x, y, z are ignored) is matched to the room's
+    points ``scene_pts`` (n, 3) by nearest neighbour; cloud k paints its matches with instance k and class ``class_ids[k]``, a
+    later cloud over an earlier one (the maximum cloud number per point).  The points no cloud reached take the labels of their
+    nearest painted point, and the instance numbers are remapped to contiguous ranks.  One index over the room serves every cloud
+    (box2mask_amd.neighbors); a second one over the painted points serves the rest.
+
+    Returns ``(instances float32 (n, 1), semantics float32 (n, 1), error)`` with the reference's dtypes and shapes, on the device;
+    ``error`` is the fp64 sum of the match distances (a float), which the reference accumulates and drops.  The mapping from file
+    names to classes (``stairs`` -> ``clutter``) and the ORDER of the clouds -- the reference takes it from an unsorted glob --
+    stay with the caller.  Exactly equidistant candidates resolve to the lowest row, where the reference's k-d tree picks by
+    traversal."""
+    from .neighbors import NearestIndex
+    index = NearestIndex(torch.as_tensor(np.ascontiguousarray(scene_pts) if isinstance(scene_pts, np.ndarray) else scene_pts)[:, :3])
+    dev = index.device
+    n = index.n
+    if len(instance_clouds) != len(class_ids):
+        raise ValueError('s3dis_point_labels: %d clouds for %d class ids' % (len(instance_clouds), len(class_ids)))
+    if n == 0 or len(instance_clouds) == 0:
+        raise ValueError('s3dis_point_labels: a room without points or without annotation clouds')
+    classes = _dev(np.asarray(class_ids), torch.int64, dev)
+    inst = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    error = torch.zeros((), dtype=torch.float64, device=dev)
+    unmatched = torch.zeros((), dtype=torch.bool, device=dev)
+    for k, cloud in enumerate(instance_clouds):
+        cloud = torch.as_tensor(np.ascontiguousarray(cloud) if isinstance(cloud, np.ndarray) else cloud)
+        dist, idx = index.query(cloud.reshape(-1, cloud.shape[-1])[:, :3], return_distance=True)
+        unmatched |= (idx < 0).any()
+        inst.scatter_reduce_(0, idx.clamp(min=0), torch.full_like(idx, k), 'amax')
+        error += dist.sum()
+    if bool(unmatched.item()):
+        raise ValueError('s3dis_point_labels: non-finite coordinates in the room or in an annotation cloud')
+    decided = inst >= 0
+    rest = torch.nonzero(~decided).reshape(-1)
+    if rest.numel():
+        rows = torch.nonzero(decided).reshape(-1)
+        near = NearestIndex(index.ref[rows]).query(index.ref[rest])
+        if bool((near < 0).any().item()):
+            raise ValueError('s3dis_point_labels: non-finite coordinates in the room')
+        inst[rest] = inst[rows[near]]
+    semantics = classes[inst].to(torch.float32).reshape(n, 1)
+    _, rank = torch.unique(inst, sorted=True, return_inverse=True)
+    return rank.to(torch.float32).reshape(n, 1), semantics, float(error.item())

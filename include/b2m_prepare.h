@@ -158,6 +158,28 @@ int b2m_inst_boxes(const double* pos, const int64_t* instances, const int64_t* s
                    uint64_t* acc, double* centers64, int32_t* per_sem, float* per_centers, float* per_bounds,
                    float* per_radius, float* offsets, float* distances, int32_t* missing, void* stream);
 
+/* ---- exact 1-nearest-neighbour index (box2mask_amd/neighbors.py, csrc/neighbors.hip): the search the reference runs through
+ * NearestNeighbors(n_neighbors=1, algorithm='ball_tree') and scipy's KDTree (dataprocessing/prepare_s3dis.py:77-104, the
+ * sparse-to-dense lookup of models/evaluation.py:154), as one general operation.  The rows are binned into a uniform grid over the
+ * bounding box of the finite rows -- at most 4 n_ref + 8 cells whatever the extent -- and sorted by (cell, row).  d2 = (dx*dx +
+ * dy*dy) + dz*dz in fp64 without contraction (the ball tree's reduced distance); equal d2 resolves to the LOWEST row (the trees'
+ * order there is a traversal artefact).  No floating-point atomics: the same bits on every run. ---- */
+
+/* Bytes of workspace for an index over n_ref rows, or a negative value when n_ref is out of range (0 <= n_ref < 2^29). */
+int64_t b2m_nn_workspace(int64_t n_ref);
+
+/* Builds the index of ref (n_ref,3) into workspace (b2m_nn_workspace(n_ref) bytes, 256-byte aligned).  Non-finite rows are
+ * indexed nowhere.  n_ref == 0 launches nothing.  No synchronisation. */
+int b2m_nn_build(const double* ref, int64_t n_ref, void* workspace, void* stream);
+
+/* idx[j] = the row of ref nearest to q[j] (q: (n_q,3)), dist[j] = sqrt(d2) (dist may be NULL).  workspace: what b2m_nn_build
+ * left for the same ref and n_ref; it is only read, so one build serves any number of queries (the rows themselves are read from the
+ * sorted copy the workspace holds; ref names the array they index).  A non-finite query gets
+ * idx = -1 and dist = NaN, and so does every query when no row of ref is finite; n_ref == 0 fills idx with -1 and dist with NaN
+ * without a launch, n_q == 0 does nothing. */
+int b2m_nn_query(const double* ref, int64_t n_ref, const void* workspace, const double* q, int64_t n_q, int32_t* idx,
+                 double* dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -809,7 +809,7 @@ S3DIS_GRID = 1.0 / 128.0
 S3DIS_NORMALS = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float64)
 
 
-def s3dis_room(rng, ri):
+def s3dis_room(rng, ri, planes=(5000, 5000, 3600, 3400, 2200), per_object=(700, 1000)):
     """One synthetic S3DIS-shaped room on an integer grid of 1/128 m with axis normals: ceiling, floor, two large walls, a wall of
     fewer than 3000 points, furniture of classes 3 .. 12 (room 2 has no class 12), predicted semantics with a few wrong points
     (some of them stray `wall` points) and proposals that the merge accepts or rejects by each of its three tests."""
@@ -821,17 +821,17 @@ def s3dis_room(rng, ri):
         g[:, axis] = value
         parts.append((g, np.full(m, normal), cls, inst))
 
-    plane(5000, 2, H, (0, 0, 0), (L, W, 0), 5, 0, 0)
-    plane(5000, 2, 0, (0, 0, 0), (L, W, 0), 4, 1, 1)
-    plane(3600, 1, 0, (0, 0, 0), (L, 0, H), 2, 2, 2)
-    plane(3400, 0, 0, (0, 0, 0), (0, W, H), 0, 2, 3)
-    plane(2200, 1, W, (0, 0, 0), (L, 0, H), 3, 2, 4)
+    plane(planes[0], 2, H, (0, 0, 0), (L, W, 0), 5, 0, 0)
+    plane(planes[1], 2, 0, (0, 0, 0), (L, W, 0), 4, 1, 1)
+    plane(planes[2], 1, 0, (0, 0, 0), (L, 0, H), 2, 2, 2)
+    plane(planes[3], 0, 0, (0, 0, 0), (0, W, H), 0, 2, 3)
+    plane(planes[4], 1, W, (0, 0, 0), (L, 0, H), 3, 2, 4)
     classes = list(range(3, 13)) + [5] if ri < 2 else list(range(3, 12)) + [5]
     boxes = []
     for i, cls in enumerate(classes):
         cx, cy = 90 + (i % 4) * 150, 90 + (i // 4) * 150
         sx, sy, sz = (int(v) for v in rng.integers(35, 60, 3))
-        m = int(rng.integers(700, 1000))
+        m = int(rng.integers(per_object[0], per_object[1]))
         g = np.stack([rng.integers(cx - sx, cx + sx + 1, m), rng.integers(cy - sy, cy + sy + 1, m), rng.integers(1, 2 * sz, m)], 1)
         parts.append((g, rng.integers(0, 6, m), cls, 5 + i))
         boxes.append((cx, cy, sx, sy))
@@ -889,18 +889,9 @@ def s3dis_dbscan_case(seed, eps=0.2, min_samples=5, sig=0.09, sep=2.5, ncl=80, p
     return x[rng.permutation(len(x))], eps, min_samples
 
 
-def gen_s3dis():
-    """S3DIS evaluation: tests/golden/eval_s3dis.npz from the reference's own code, imported unmodified -- utils/s3dis_util.py
-    (clustering_for_background, assign_semantics_to_proposals, s3dis_eval; sklearn's DBSCAN inside) and Evaluater.s3dis_eval
-    (models/evaluation.py:124-241), which is DRIVEN here for the merge stage: a fake model hands it the fixture's per-voxel logits
-    and masks, a list is the loader, s3dis.get_scene_names is a stub and s3dis_util's three functions are wrapped to record what
-    goes through them.  pyviz3d, quaternion, natsort and tensorboard get empty stand-ins where missing; np.float (gone from numpy)
-    is restored in this process only.  The fixture holds data only: positions as int16 steps of 1/128 m, normals as indices into
-    the six axis directions, masks bit-packed."""
-    import contextlib
-    import io
-    sys.path.insert(0, os.path.join(ROOT, 'tests'))
-    from _s3dis_rule import dbscan_rule, margin
+def _s3dis_eval_modules():
+    """models/evaluation.py and utils/s3dis_util.py of the reference, imported unmodified behind the stand-ins gen_s3dis describes;
+    also the stand-in of dataprocessing.s3dis the evaluation module reads its scene names (and the unsampled rooms) through."""
     D = _dataloader_module()
     for name in ('pyviz3d', 'pyviz3d.visualizer', 'quaternion', 'natsort', 'tensorboard', 'torch.utils.tensorboard'):
         try:
@@ -923,6 +914,26 @@ def gen_s3dis():
     s3.ID2NAME = ['class%d' % c for c in range(13)]
     import models.evaluation as EV
     import utils.s3dis_util as SU
+    if EV.s3dis is not s3:                           # imported by an earlier target: it holds that target's stand-in
+        s3 = EV.s3dis
+        s3.get_scene_names = lambda mode, cfg: []
+        s3.ID2NAME = ['class%d' % c for c in range(13)]
+    return EV, SU, s3
+
+
+def gen_s3dis():
+    """S3DIS evaluation: tests/golden/eval_s3dis.npz from the reference's own code, imported unmodified -- utils/s3dis_util.py
+    (clustering_for_background, assign_semantics_to_proposals, s3dis_eval; sklearn's DBSCAN inside) and Evaluater.s3dis_eval
+    (models/evaluation.py:124-241), which is DRIVEN here for the merge stage: a fake model hands it the fixture's per-voxel logits
+    and masks, a list is the loader, s3dis.get_scene_names is a stub and s3dis_util's three functions are wrapped to record what
+    goes through them.  pyviz3d, quaternion, natsort and tensorboard get empty stand-ins where missing; np.float (gone from numpy)
+    is restored in this process only.  The fixture holds data only: positions as int16 steps of 1/128 m, normals as indices into
+    the six axis directions, masks bit-packed."""
+    import contextlib
+    import io
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from _s3dis_rule import dbscan_rule, margin
+    EV, SU, s3 = _s3dis_eval_modules()
     from sklearn.cluster import DBSCAN
 
     out = {}
@@ -1044,6 +1055,245 @@ def gen_s3dis():
     _savez_fixed(path, out)
     assert os.path.getsize(path) <= 1000000, os.path.getsize(path)
     print('eval_s3dis.npz: %d bytes; rooms 0-1 mPrec %.4f mRec %.4f; room 2 alone mPrec %s' % (os.path.getsize(path), both[0], both[1], alone[0]))
+
+
+def gen_s3dis_labels():
+    """Label transfer of the raw S3DIS dataset: tests/golden/s3dis_labels.npz from the reference's own get_labels
+    (dataprocessing/prepare_s3dis.py:71-121), imported unmodified.  The module parses its arguments and runs its main loop on
+    import, so it is imported with a patched sys.argv whose --data_dir is an empty directory (the loop finds no room), behind
+    stand-ins for skimage, open3d, pyviz3d, natsort and configargparse (argparse's parser) where they are missing.  get_labels then
+    runs over a temporary directory of synthetic Annotations/*.txt files with glob.glob wrapped to return a sorted list (the
+    reference takes the order of an unsorted glob) and scipy's KDTree wrapped to record the match distances, whose sum the
+    reference accumulates and drops; np.loadtxt is called with ndmin=2 meanwhile, because get_labels cannot index the vector a
+    file of ONE row loads as, and the fixture has a cloud of one point.  The fixture holds what the reference loaded -- the room's points and every cloud after
+    np.loadtxt, the file names -- and what it returned."""
+    import argparse
+    import glob as glob_module
+    import importlib
+    import tempfile
+    for name in ('skimage', 'skimage.io', 'open3d', 'pyviz3d', 'pyviz3d.visualizer', 'natsort', 'configargparse'):
+        try:
+            __import__(name)
+        except Exception:
+            sys.modules[name] = types.ModuleType(name)
+    sys.modules['skimage'].io = sys.modules['skimage.io']
+    sys.modules['pyviz3d'].visualizer = sys.modules['pyviz3d.visualizer']
+    if not hasattr(sys.modules['natsort'], 'natsorted'):
+        sys.modules['natsort'].natsorted = sorted
+    if not hasattr(sys.modules['configargparse'], 'ArgumentParser'):
+        sys.modules['configargparse'].ArgumentParser = argparse.ArgumentParser
+    for name in [k for k in sys.modules if k == 'dataprocessing' or k.startswith('dataprocessing.')]:
+        del sys.modules[name]                                   # the empty stand-ins of the other targets
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+
+    rng = np.random.default_rng(4711)
+    # name of the annotation file, points; sorted by name this is the order of the clouds
+    sizes = [('beam_1', 150), ('board_1', 1), ('ceiling_1', 400), ('chair_1', 3), ('chair_2', 220), ('clutter_1', 180),
+             ('floor_1', 400), ('stairs_1', 120), ('table_1', 200), ('wall_1', 350)]
+    centres = rng.uniform(0, 1, (len(sizes), 3)) * np.array([8.0, 6.0, 3.0])
+    clouds = [np.round(c + rng.normal(0, 0.4, (m, 3)), 6) for (_, m), c in zip(sizes, centres)]
+    scene = np.concatenate(clouds)                              # the room file is the concatenation of its annotations ...
+    scene = np.concatenate([scene, np.round(rng.uniform(-1, 1, (600, 3)) * 0.5 + scene[rng.integers(0, len(scene), 600)], 6)])
+    scene = scene[rng.permutation(len(scene))]                  # ... here with 600 points that are in no cloud, in shuffled order
+    assert len(np.unique(scene, axis=0)) == len(scene)
+    # chair_1's three points are chair_2's first three: its id disappears in the remap; table_1 claims a point of clutter_1 and wall_1
+    # one of floor_1; a fifth of every larger cloud is off its scene point by up to 2 mm (a match distance above zero)
+    clouds[4][:3] = clouds[3]
+    clouds[8][0] = clouds[5][0]
+    clouds[9][0] = clouds[6][0]
+    for c in clouds:
+        if len(c) >= 100:
+            k = len(c) // 5
+            c[-k:] = np.round(c[-k:] + rng.uniform(-0.002, 0.002, (k, 3)), 6)
+
+    with tempfile.TemporaryDirectory() as tmp:
+        empty = os.path.join(tmp, 'empty'); os.makedirs(empty)
+        ann = os.path.join(tmp, 'data', 'Area_9', 'room_1', 'Annotations'); os.makedirs(ann)
+        for (name, _), c in zip(sizes, clouds):
+            np.savetxt(os.path.join(ann, name + '.txt'), np.concatenate([c, rng.integers(0, 256, (len(c), 3))], 1), fmt='%.6f')
+        np.savetxt(os.path.join(tmp, 'room_1.txt'), np.concatenate([scene, rng.integers(0, 256, (len(scene), 3))], 1), fmt='%.6f')
+        argv = sys.argv
+        sys.argv = ['prepare_s3dis.py', '--data_dir', empty]
+        try:
+            PS = importlib.import_module('dataprocessing.prepare_s3dis')
+        finally:
+            sys.argv = argv
+        seen = []
+        real_tree, real_glob, real_loadtxt = PS.KDTree, glob_module.glob, np.loadtxt
+
+        class Tree(real_tree):
+            def query(self, *a, **k):
+                r = super().query(*a, **k)
+                seen.append((np.array(r[0], copy=True), np.array(r[1], copy=True)))
+                return r
+
+        PS.KDTree = Tree
+        glob_module.glob = lambda *a, **k: sorted(real_glob(*a, **k))
+        np.loadtxt = lambda pth: real_loadtxt(pth, ndmin=2)        # (a file of one row loads as a vector, which get_labels cannot index)
+        try:
+            scene_data = np.loadtxt(os.path.join(tmp, 'room_1.txt'))
+            paths = glob_module.glob(ann + '/*.txt')
+            loaded = [np.loadtxt(pth) for pth in paths]
+            instances, semantics = PS.get_labels('Area_9.room_1', scene_data, os.path.join(tmp, 'data'))
+        finally:
+            PS.KDTree, glob_module.glob, np.loadtxt = real_tree, real_glob, real_loadtxt
+    names = [os.path.basename(pth)[:-4] for pth in paths]
+    assert names == [n for n, _ in sizes] and len(seen) == len(sizes) + 1
+    class_ids = np.array([PS.NAME2ID['clutter' if n.split('_')[0] == 'stairs' else n.split('_')[0]] for n in names], np.int64)
+    pts = scene_data[:, :3]
+    # what the fixture must contain, and that no match is decided by a tie (the k-d tree's choice there is an artefact)
+    claims = np.zeros(len(pts), np.int64)
+    for (d, i) in seen[:-1]:
+        claims[np.unique(i)] += 1
+    assert (claims == 0).sum() >= 500 and (claims >= 2).sum() >= 3 and min(len(c) for c in loaded) == 1
+    assert len(np.unique(instances)) == len(sizes) - 1 and instances.max() == len(sizes) - 2
+    assert instances.dtype == np.float32 and semantics.dtype == np.float32 and instances.shape == semantics.shape == (len(pts), 1)
+    decided = claims > 0
+    for qs, rs in [(c[:, :3], pts) for c in loaded] + [(pts[~decided], pts[decided])]:
+        dx, dy, dz = (qs[:, None, j] - rs[None, :, j] for j in range(3))
+        d2 = np.sort((dx * dx + dy * dy) + dz * dz, 1)[:, :2]
+        assert (d2[:, 1] - d2[:, 0] > 1e-9 * d2[:, 0]).all(), 'a match within a relative 1e-9 of a tie'
+    error = 0
+    for (d, i) in seen[:-1]:
+        error += d.sum()                                          # prepare_s3dis.py:98
+    assert error > 0
+    out = {'scene_pts': pts, 'names': np.array(names), 'class_ids': class_ids, 'instances': instances, 'semantics': semantics,
+           'error': np.float64(error), 'n_clouds': np.array(len(loaded))}
+    for k, c in enumerate(loaded):
+        out['cloud%d' % k] = c.reshape(-1, 6)[:, :3]
+    path = os.path.join(OUT, 's3dis_labels.npz')
+    _savez_fixed(path, out)
+    assert os.path.getsize(path) <= 1000000, os.path.getsize(path)
+    print('s3dis_labels.npz: %d bytes; %d points, %d in no cloud, %d claimed twice, error %.6f'
+          % (os.path.getsize(path), len(pts), (claims == 0).sum(), (claims >= 2).sum(), error))
+
+
+def s3dis_full_room(rng, ri):
+    """A room for the full-resolution evaluation: the SAMPLED room is an s3dis_room of about 11 000 points (one wall large enough
+    to survive the 3000-point rule); the full room has four times as many, rows [::4] being the sampled ones as the reference
+    samples, the others copies of random sampled points moved by up to two grid steps per axis, with their source's ground truth.
+    No two sampled points coincide and no full point has two nearest sampled points at the same distance (checked exactly, on the
+    integer grid): the trees' choice there is a traversal artefact."""
+    grid, normal, gt_sem, gt_ins, pred, masks = s3dis_room(rng, ri, planes=(300, 500, 3300, 200, 150), per_object=(520, 640))
+    grid = grid.astype(np.int64)
+    while True:
+        _, first = np.unique(grid, axis=0, return_index=True)
+        dup = np.setdiff1d(np.arange(len(grid)), first)
+        if len(dup) == 0:
+            break
+        grid[dup] = np.maximum(grid[dup] + rng.integers(-2, 3, (len(dup), 3)), 0)
+    n = len(grid)
+    full = np.zeros((4 * n, 3), np.int64)
+    src = np.zeros(4 * n, np.int64)
+    src[0::4] = np.arange(n)
+    full[0::4] = grid
+    todo = np.nonzero(np.arange(4 * n) % 4 != 0)[0]
+    while len(todo):
+        src[todo] = rng.integers(0, n, len(todo))
+        full[todo] = np.maximum(grid[src[todo]] + rng.integers(-2, 3, (len(todo), 3)), 0)
+        tied = []
+        for s in range(0, len(todo), 2048):
+            rows = todo[s:s + 2048]
+            d2 = ((full[rows, None, :] - grid[None, :, :]) ** 2).sum(2)
+            two = np.partition(d2, 1, axis=1)[:, :2]
+            tied.append(rows[two[:, 0] == two[:, 1]])
+        todo = np.concatenate(tied)
+    return dict(grid=grid.astype(np.int16), normal=normal, gt_sem=gt_sem, gt_ins=gt_ins, pred=pred, masks=masks,
+                full=full.astype(np.int16), full_sem=gt_sem[src], full_ins=gt_ins[src])
+
+
+def gen_s3dis_full():
+    """Full-resolution S3DIS evaluation: tests/golden/eval_s3dis_full.npz from Evaluater.s3dis_eval driven as in gen_s3dis, with
+    cfg.full_resolution = True, s3dis.process_scene replaced by a function that returns the full room, and get_sparse2dense --
+    which the reference calls (evaluation.py:154) and defines nowhere -- put into the evaluation module's namespace as the sklearn
+    ball-tree lookup of the nearest sampled point.  The sampled room is rows [::4] of the full one.  Data only: positions as int16
+    steps of 1/128 m, normals as indices into the six axis directions, masks bit-packed."""
+    import contextlib
+    import io
+    from sklearn.neighbors import NearestNeighbors
+    EV, SU, s3 = _s3dis_eval_modules()
+    rng = np.random.default_rng(2025)
+    rooms = [s3dis_full_room(rng, ri) for ri in range(2)]
+    batches, by_name, full_by_name = [], {}, {}
+    for ri, rm in enumerate(rooms):
+        name = 'room%d' % ri
+        full_pos = rm['full'].astype(np.float64) * S3DIS_GRID
+        scene = {'name': name, 'positions': full_pos[::4], 'normals': S3DIS_NORMALS[rm['normal']]}
+        assert np.array_equal(scene['positions'], rm['grid'].astype(np.float64) * S3DIS_GRID)
+        labels = {'semantics': rm['gt_sem'], 'instances': rm['gt_ins']}
+        batches.append({'scene': [scene], 'labels': [labels], 'vox2point': [np.arange(len(rm['grid']))]})
+        by_name[name] = (rm['pred'], rm['masks'])
+        full_by_name[name] = ({'name': name, 'positions': full_pos}, {'semantics': rm['full_sem'], 'instances': rm['full_ins']})
+
+    class FakeModel:
+        def get_prediction(self, batch, with_grad=False, to_cpu=True, min_size=True):
+            pred, _ = by_name[batch['scene'][0]['name']]
+            return {'mlp_per_vox_semantics': torch.from_numpy(np.eye(13, dtype=np.float32)[pred])}
+
+        def pred2mask(self, batch, prediction, mode='eval'):
+            name = batch['scene'][0]['name']
+            return {name: {'mask': by_name[name][1].astype(np.uint8)}}
+
+    seen = {'s2d': []}
+    real_eval = SU.s3dis_eval
+
+    def ev(pred_labels, gt_labels):
+        seen['pred_labels'], seen['gt_labels'] = pred_labels, gt_labels
+        with np.errstate(all='ignore'):
+            seen['result'] = real_eval(pred_labels, gt_labels)
+        return seen['result']
+
+    def get_sparse2dense(scene_full, scene, cfg):
+        tree = NearestNeighbors(n_neighbors=1, algorithm='ball_tree').fit(scene['positions'])
+        s2d = tree.kneighbors(scene_full['positions'], return_distance=False)[:, 0]
+        seen['s2d'].append(s2d)
+        return s2d
+
+    SU.s3dis_eval = ev
+    EV.get_sparse2dense = get_sparse2dense
+    s3.process_scene = lambda name, mode, cfg: full_by_name[name]
+    evaluater = object.__new__(EV.Evaluater)
+    evaluater.model = FakeModel()
+    evaluater.cfg = SimpleNamespace(eval_ths=[0.5, 0.03, 0.3, 0.6], s3dis_split_fold=5, full_resolution=True, point_sampling_rate=4)
+    loader = SimpleNamespace(get_loader=lambda **kw: batches)
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            evaluater.s3dis_eval(loader)
+    finally:
+        SU.s3dis_eval = real_eval
+        del EV.get_sparse2dense, s3.process_scene
+    assert evaluater.cfg.point_sampling_rate is None                                   # evaluation.py:152
+    mprec, mrec, prec, rec = seen['result']
+    assert np.isfinite(mprec) and np.isfinite(mrec) and 0 < mprec < 1 and 0 < mrec < 1
+    out = {'n_rooms': np.array(2), 'mprec': np.float64(mprec), 'mrec': np.float64(mrec), 'precision': np.asarray(prec, np.float64),
+           'recall': np.asarray(rec, np.float64)}
+    for ri, rm in enumerate(rooms):
+        s2d, fin, gt = seen['s2d'][ri], seen['pred_labels'][ri], seen['gt_labels'][ri]
+        n, nf = len(rm['grid']), len(rm['full'])
+        assert nf == 4 * n and np.array_equal(s2d[::4], np.arange(n)) and (s2d != np.arange(nf) // 4).sum() > nf // 4
+        assert len(fin['instances']) == nf and len(gt['instances']) == nf
+        ins = np.asarray(fin['instances'])
+        walls = (np.asarray(fin['semantics']) == 2) & (ins > 0)
+        assert walls.sum() >= 4 * 3000 * 0.9 and len(np.unique(ins[ins >= 0])) >= 8, 'the large wall or the proposals did not survive'
+        out['r%d_full' % ri] = rm['full']; out['r%d_sampled' % ri] = rm['grid']; out['r%d_normal' % ri] = rm['normal']
+        out['r%d_pred_semantics' % ri] = rm['pred'].astype(np.int8)
+        out['r%d_masks' % ri] = np.packbits(rm['masks'], axis=1)
+        out['r%d_gt_semantics' % ri] = rm['gt_sem'].astype(np.int8); out['r%d_gt_instances' % ri] = rm['gt_ins'].astype(np.int8)
+        out['r%d_sparse2dense' % ri] = s2d.astype(np.int16)
+        out['r%d_full_pred_semantics' % ri] = np.asarray(fin['semantics']).astype(np.int8)
+        out['r%d_full_pred_instances' % ri] = ins.astype(np.int8)
+        out['r%d_full_gt_semantics' % ri] = np.asarray(gt['semantics']).astype(np.int8)
+        out['r%d_full_gt_instances' % ri] = np.asarray(gt['instances']).astype(np.int8)
+        for k in ('full_pred_semantics', 'full_pred_instances', 'full_gt_semantics', 'full_gt_instances'):
+            src = {'full_pred_semantics': fin['semantics'], 'full_pred_instances': ins, 'full_gt_semantics': gt['semantics'],
+                   'full_gt_instances': gt['instances']}[k]
+            assert np.array_equal(out['r%d_%s' % (ri, k)], np.asarray(src)), k         # (nothing lost in the narrow types)
+    path = os.path.join(OUT, 'eval_s3dis_full.npz')
+    _savez_fixed(path, out)
+    assert os.path.getsize(path) <= 1000000, os.path.getsize(path)
+    print('eval_s3dis_full.npz: %d bytes; %s full points; mPrec %.4f mRec %.4f'
+          % (os.path.getsize(path), [len(rm['full']) for rm in rooms], mprec, mrec))
 
 
 def gen_augment():
@@ -1199,7 +1449,8 @@ def gen_augment():
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
-    which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval', 'detection', 's3dis', 'augment']
+    which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval', 'detection', 's3dis', 'augment',
+                             's3dis_labels', 's3dis_full']
     if 'iou_nms' in which:
         gen_iou_nms()
     if 'detection2mask' in which:
@@ -1220,3 +1471,7 @@ if __name__ == '__main__':
         gen_s3dis()
     if 'augment' in which:
         gen_augment()
+    if 's3dis_labels' in which:
+        gen_s3dis_labels()
+    if 's3dis_full' in which:
+        gen_s3dis_full()
