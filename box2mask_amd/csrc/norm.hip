@@ -1,5 +1,9 @@
 // BatchNorm statistics / apply / backward, small elementwise ops and segment pooling.
 // All HBM-bound: float4 accesses, one pass per tensor, deterministic two-stage column reductions.
+// Precision contract (tests/_norm_rule.py holds every path to it): the BatchNorm STATISTICS are fp64 sums of the fp32 inputs on
+// every path -- bn_stats_kernel, bn_small_fwd_kernel, the convolution's tile sums -- and the finalize math is fp64, one rounding per
+// fp32 constant.  The BACKWARD sums (sum g, sum g * xhat) go through the skeleton below: fp32 chains of at most 64 terms per
+// thread, fp64 from there on (the one-launch kernels: fp64 throughout).  The binary16 statistics kernel keeps the fp32 chains.
 #include "b2m_common.h"
 
 #define RED_MAX_BLOCKS 1280   // 256 CUs x 5 resident blocks of bn_bwd_reduce: one full round, no tail (4096: 12 % slower)
@@ -53,9 +57,13 @@ __device__ __forceinline__ void column_reduce(int64_t n, int c, double* __restri
 // `f(in, a, b)` turns them into the two contributions.  In column_reduce the functor loads and computes, and with
 // wave-uniform branches inside it hipcc waited for every row's data before issuing the next row's loads: two or three
 // 16-byte loads in flight per thread, 3.5 TB/s; staged, eight to twelve.
-template <int NIN, class L, class F>
+// ACC: the type a thread accumulates in and the block's LDS slots hold -- float (fp32 chains of at most 64 terms for c <= 256,
+// n <= 327 680; fp64 from the block combine on) or double (`f` then fills double4 contributions: the BatchNorm statistics).
+template <int NIN, class ACC = float, class L, class F>
 __device__ __forceinline__ void column_reduce_staged(int64_t n, int c, double* __restrict__ partial, L load, F f) {
-    extern __shared__ float red[];             // [nslots][c4][8]
+    typedef ACC acc4 __attribute__((ext_vector_type(4)));
+    extern __shared__ __attribute__((aligned(16))) unsigned char red_raw[];
+    ACC* red = (ACC*)red_raw;                  // [nslots][c4][8]
     const int c4 = c >> 2;
     const int nslots = 256 / c4;
     const int cg = threadIdx.x % c4, rs = threadIdx.x / c4;
@@ -63,7 +71,7 @@ __device__ __forceinline__ void column_reduce_staged(int64_t n, int c, double* _
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_blk;
     int64_t r1 = r0 + rows_per_blk;
     if (r1 > n) r1 = n;
-    f32x4 sa = {0, 0, 0, 0}, sb = {0, 0, 0, 0};
+    acc4 sa = {0, 0, 0, 0}, sb = {0, 0, 0, 0};
     if (rs < nslots) {
         int64_t r = r0 + rs;
         for (; r + 3 * nslots < r1; r += 4 * nslots) {
@@ -73,25 +81,26 @@ __device__ __forceinline__ void column_reduce_staged(int64_t n, int c, double* _
             __builtin_amdgcn_sched_barrier(0);         // (left alone, the scheduler sinks each load to its first use)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                f32x4 a, b;
+                acc4 a, b;
                 f(in[u], a, b);
                 sa += a; sb += b;
             }
         }
         for (; r < r1; r += nslots) {
-            f32x4 in[NIN], a, b;
+            f32x4 in[NIN];
+            acc4 a, b;
             load(r, cg, in);
             f(in, a, b);
             sa += a; sb += b;
         }
-        float* p = red + ((size_t)rs * c4 + cg) * 8;
-        *(f32x4*)p = sa; *(f32x4*)(p + 4) = sb;
+        ACC* p = red + ((size_t)rs * c4 + cg) * 8;
+        *(acc4*)p = sa; *(acc4*)(p + 4) = sb;
     }
     __syncthreads();
     if (rs == 0) {
         double da[4] = {0, 0, 0, 0}, db[4] = {0, 0, 0, 0};
         for (int s = 0; s < nslots; ++s) {
-            const float* p = red + ((size_t)s * c4 + cg) * 8;
+            const ACC* p = red + ((size_t)s * c4 + cg) * 8;
 #pragma unroll
             for (int u = 0; u < 4; ++u) { da[u] += (double)p[u]; db[u] += (double)p[4 + u]; }
         }
@@ -125,11 +134,18 @@ static int reduce_blocks(int64_t n) {
 }
 
 // ------------------------------------------------------------------ BN forward
+// Statistics from x: the skeleton with FP64 accumulators -- every element is widened before it is added, and x * x is exact in a
+// double -- as bn_small_fwd_kernel and the convolution's tile sums do.  The variance is the difference of the two sums: with fp32
+// chains a column whose |mean| is 100 sigma loses about 160 ulps of invstd and one at 1000 sigma 7e-4 relative (SIMULATED in numpy
+// with this launch geometry, not measured on a device; tests/test_norm_rule.py repeats the simulation with chains of 25 rows).  With
+// fp64 sums every path rounds to the fp32 constants of the exact value.  Three fp64 operations per element loaded: HBM-bound.
+// (The binary16 twin and the backward sums keep fp32 chains.)
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int c,
                                                        double* __restrict__ partial) {
-    column_reduce_staged<1>(n, c, partial,
+    typedef double f64x4 __attribute__((ext_vector_type(4)));
+    column_reduce_staged<1, double>(n, c, partial,
         [&](int64_t r, int cg, f32x4 (&in)[1]) { in[0] = *(const f32x4*)(x + r * ldx + cg * 4); },
-        [&](const f32x4 (&in)[1], f32x4& a, f32x4& b) { a = in[0]; b = in[0] * in[0]; });
+        [&](const f32x4 (&in)[1], f64x4& a, f64x4& b) { a = __builtin_convertvector(in[0], f64x4); b = a * a; });
 }
 extern "C" int b2m_bn_stats(const float* x, int64_t ldx, int64_t n, int32_t c, double* partial, double* stats,
                             void* stream) {
@@ -139,7 +155,7 @@ extern "C" int b2m_bn_stats(const float* x, int64_t ldx, int64_t n, int32_t c, d
     B2M_CHECK_ARG(((uintptr_t)x % 16) == 0, "x must be 16-byte aligned");
     const int nblk = reduce_blocks(n);
     const int c4 = c / 4, nslots = 256 / c4;
-    bn_stats_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(float), st>>>(x, ldx, n, c, partial);
+    bn_stats_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(double), st>>>(x, ldx, n, c, partial);
     reduce_final_kernel<<<2 * c, 64, 0, st>>>(partial, nblk, 2 * c, stats, nullptr, nullptr);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
@@ -218,7 +234,7 @@ extern "C" int b2m_bn_stats_finalize(const float* x, int64_t ldx, int64_t n, int
     B2M_CHECK_ARG(((uintptr_t)x % 16) == 0 && n >= 1, "x must be 16-byte aligned, n >= 1");
     const int nblk = reduce_blocks(n);
     const int c4 = c / 4, nslots = 256 / c4;
-    bn_stats_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(float), st>>>(x, ldx, n, c, partial);
+    bn_stats_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(double), st>>>(x, ldx, n, c, partial);
     bn_final_finalize_kernel<<<c, 64, 0, st>>>(partial, nblk, (double)n, c, gamma, beta, eps, momentum, running_mean,
                                                running_var, mean, invstd, scale, shift, stats);
     B2M_LAUNCH_CHECK();
@@ -915,7 +931,7 @@ extern "C" int b2m_bn_bwd_apply2(const float* dy, int64_t lddy, const float* y, 
 // not bandwidth -- 38 of the 89 BatchNorm layers of a ScanNet step have <= 4 k rows.  Here one workgroup owns FOUR
 // channels (one 16-byte column group) for ALL rows: pass 1 sums in fp64 per thread (thread = row slot, fixed order), the
 // block combines in a fixed tree, the finalize math runs in the block, pass 2 re-reads the rows (L2 hits) and writes.
-// Deterministic; the statistics are fp64 sums of the fp32 inputs exactly like the two-stage kernels (other grouping).
+// Deterministic; the statistics are fp64 sums of the fp32 inputs exactly like bn_stats_kernel's (other grouping).
 #define BN_SMALL_THREADS 256
 // block-wide sum of NV doubles per thread -> every thread gets the totals (fixed order: lanes by shuffle, waves in order)
 template <int NV>
@@ -1259,8 +1275,9 @@ __global__ __launch_bounds__(256) void pool_mean_sorted_kernel(const float* __re
 extern "C" int b2m_segment_mean_sorted(const float* x, int64_t ldx, int64_t n, int32_t c, const int64_t* order,
                                        const int64_t* seg_start, int64_t n_seg, float* out, int32_t* counts,
                                        void* stream) {
-    B2M_CHECK_ARG(x && order && seg_start && out && counts && c > 0 && ldx >= c && n >= 0 && n_seg >= 0, "bad arguments");
+    B2M_CHECK_ARG(c > 0 && n >= 0 && n_seg >= 0, "bad arguments");
     if (n_seg == 0) return B2M_OK;
+    B2M_CHECK_ARG(((x && order && ldx >= c) || n == 0) && seg_start && out && counts, "bad arguments");
     B2M_CHECK_ARG(n_seg < (1ll << 31), "too many segments");
     pool_mean_sorted_kernel<<<(unsigned)n_seg, (unsigned)(c >= 256 ? 256 : (c + 63) / 64 * 64), 0, (hipStream_t)stream>>>(
         x, ldx, c, order, seg_start, out, counts);
@@ -1306,9 +1323,12 @@ extern "C" int b2m_segment_pool_fwd(const float* x, int64_t ldx, int64_t n, int3
                                     int64_t n_seg, int32_t mode, float* out, int32_t* counts, int32_t* argmax,
                                     uint64_t* scratch, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(x && ids && out && counts && c > 0 && ldx >= c && n_seg >= 0, "bad arguments");
-    B2M_CHECK_ARG(mode == 0 || (mode == 1 && argmax && scratch), "mode 1 (max) needs argmax and scratch");
+    // empty tensors have no address and no pitch: n_seg == 0 writes nothing; n == 0 leaves every segment empty (zeros, count 0,
+    // argmax -1).  The scalar arguments are checked whatever the sizes.
+    B2M_CHECK_ARG(c > 0 && n >= 0 && n_seg >= 0 && (mode == 0 || mode == 1), "bad arguments");
     if (n_seg == 0) return B2M_OK;
+    B2M_CHECK_ARG(((x && ids && ldx >= c) || n == 0) && out && counts, "bad arguments");
+    B2M_CHECK_ARG(mode == 0 || (argmax && scratch), "mode 1 (max) needs argmax and scratch");
     B2M_HIP(hipMemsetAsync(counts, 0, n_seg * sizeof(int32_t), st));
     if (mode == 0) {            // the sum kernel counts the rows per segment as it goes
         B2M_HIP(hipMemsetAsync(out, 0, (size_t)n_seg * c * sizeof(float), st));
@@ -1369,9 +1389,10 @@ extern "C" int b2m_segment_pool_bwd(const float* dout, int64_t n, int32_t c, con
                                     int32_t mode, const int32_t* counts, const int32_t* argmax, float* dx,
                                     int64_t lddx, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(dout && ids && dx && c > 0 && lddx >= c, "bad arguments");
+    B2M_CHECK_ARG(c > 0 && n >= 0 && n_seg >= 0 && (mode == 0 || mode == 1), "bad arguments");
+    if (n == 0) return B2M_OK;              // (no rows: nothing to write, and the empty tensors have no address)
+    B2M_CHECK_ARG(dout && ids && dx && lddx >= c, "bad arguments");
     B2M_CHECK_ARG((mode == 0 && counts) || (mode == 1 && argmax), "mode 0 needs counts, mode 1 needs argmax");
-    if (n == 0) return B2M_OK;
     if (c % 4 == 0 && c <= 1024 && lddx % 4 == 0 && ((uintptr_t)dout % 16) == 0 && ((uintptr_t)dx % 16) == 0 &&
         (mode == 0 || ((uintptr_t)argmax % 16) == 0))
         pool_bwd_vec_kernel<<<row_grid(n, c / 4), 256, 0, st>>>(dout, n, c / 4, ids, mode, counts, argmax, dx, lddx);

@@ -10,7 +10,7 @@ stay fp32, as do the weights (master copies, the optimizer's); every accumulatio
   mirrored) weights;
 * weight gradient: `b2m_conv_wgrad_h` (half operands converted on load, fp32 MFMA, fp32 dW);
 * BatchNorm: `b2m_bn_stats_finalize_h` -> `b2m_bn_apply_h`, backward `b2m_bn_bwd_reduce_h` -> `b2m_bn_bwd_apply_h`
-  (fp64 statistics, the ReLU mask is the sign of the stored half output);
+  (statistics: fp32 chains of at most 64 rows per thread, fp64 from there on and in the finalize math; the ReLU mask is the sign of the stored half output);
 * loss scaling: the gradient is multiplied by `loss_scale` where it enters the half region (`to_float`), every parameter gradient
   the region produces is multiplied by 1 / loss_scale by the operator that produced it, and the gradient that leaves the region
   towards the stem (`to_half`) likewise -- outside the region nothing is scaled.

@@ -366,7 +366,10 @@ int b2m_clock_probe(unsigned long long* out4, int32_t iters, void* stream);
 /* ---------------------------------------------------------------- batch norm / elementwise (fp32, HBM-bound) */
 
 /* Column sums for BatchNorm: stats[0:c] = sum x, stats[c:2c] = sum x^2 (double), deterministic
- * two-stage reduction.  partial: double[2*c*nblk_max] scratch with nblk_max = 4096.
+ * two-stage reduction.  Every term is widened to fp64 BEFORE it is added (per thread, then per block, then over the
+ * blocks), as in the one-launch kernels and the convolution's tile sums: the fp32 constants of every path are those of
+ * the exact statistics to within rounding, also for a column whose |mean| is 1000 sigma (tests/_norm_rule.py,
+ * const_bounds).  partial: double[2*c*nblk_max] scratch with nblk_max = 4096.
  * Replaces the reduction inside torch.nn.BatchNorm1d wrapped by ME.MinkowskiBatchNorm
  * (resnet.py:63,66; detection_net.py:40-135). */
 int b2m_bn_stats(const float* x, int64_t ldx, int64_t n, int32_t c, double* partial, double* stats, void* stream);
@@ -483,7 +486,9 @@ int b2m_add(const float* a, const float* b, int64_t n_elem, float* out, void* st
  * models/detection_net.py:345-352 with a direct segmented reduction (no second hash build).
  * mode 0 sums with fp32 atomics (order-dependent in the last bits) and divides by the exact integer
  * count; mode 1 is deterministic (64-bit packed atomicMax, lowest row wins ties).
- *   counts[n_seg] int32 out; argmax[n_seg*c] int32 out (mode 1 only); scratch uint64[n_seg*c] (mode 1 only) */
+ *   counts[n_seg] int32 out; argmax[n_seg*c] int32 out (mode 1 only); scratch uint64[n_seg*c] (mode 1 only)
+ * An empty segment gives 0, count 0 and argmax -1.  n == 0 is allowed (x, ids may be NULL), n_seg == 0 writes nothing.
+ * Inputs without -0.0 and NaN (the packed order puts -0.0 below +0.0). */
 int b2m_segment_pool_fwd(const float* x, int64_t ldx, int64_t n, int32_t c, const int64_t* ids, int64_t n_seg,
                          int32_t mode, float* out, int32_t* counts, int32_t* argmax, uint64_t* scratch,
                          void* stream);

@@ -174,7 +174,18 @@ def segment_pool(x: torch.Tensor, ids: torch.Tensor, n_seg: int, mode: str = 'av
     out = torch.zeros(n_seg, x.shape[1], dtype=x.dtype)
     if mode == 'avg':
         return out.scatter_reduce(0, idx, x, 'mean', include_self=False)
-    return out.scatter_reduce(0, idx, x, 'amax', include_self=False)
+    # max: the value of ONE row per (segment, channel), the lowest row among equal maxima, so the gradient goes to that row alone
+    # (scatter_reduce('amax') would split it among the ties); an empty segment gives 0 and no gradient.  That a max pooling
+    # routes its gradient to a single index is how such operators are built (an arg-max index per output); WHICH of several
+    # equal rows MinkowskiEngine picks is an ASSUMPTION here -- the engine is not available to observe
+    n = x.shape[0]
+    if n == 0 or n_seg == 0:
+        return out + x.sum() * 0                       # (all zeros, still a function of x for autograd)
+    top = out.scatter_reduce(0, idx, x.detach(), 'amax', include_self=False)
+    rows = torch.arange(n).reshape(-1, 1).expand_as(idx)
+    cand = torch.where(x.detach() == top[ids.reshape(-1)], rows, torch.full_like(rows, n))
+    arg = torch.full((n_seg, x.shape[1]), n, dtype=torch.int64).scatter_reduce(0, idx, cand, 'amin', include_self=True)
+    return torch.where(arg < n, x.gather(0, arg.clamp(max=n - 1)), out)
 
 
 # ----------------------------------------------------------------------------- coordinate hierarchy

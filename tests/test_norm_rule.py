@@ -1,0 +1,268 @@
+"""The float64 restatement of BatchNorm, segment pooling, ReLU and add (tests/_norm_rule.py) against float64 torch, its tie and
+empty-segment conventions against hand-computed cases, and its bounds against (a) an fp32 evaluation of the same formulas in an
+order unlike the kernels' -- they must not be too tight -- and (b) deliberate mistakes -- they must not be too loose -- on the very
+cases tests/test_gpu_norm.py runs.  No GPU.
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import _norm_rule as R
+
+T = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64).copy())
+
+
+def close(got, ref, what, rel=1e-9):
+    """float64 against float64: 1e-9 of the column's (or tensor's) largest magnitude -- torch forms the variance in another order,
+    and a column with |mean| = 1000 sigma loses six of the sixteen digits there."""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    top = np.abs(ref).max(0) if ref.ndim == 2 else np.abs(ref)
+    assert got.shape == ref.shape, what
+    assert np.all(np.abs(got - ref) <= rel * np.maximum(top, 1e-30)), (what, float(np.abs(got - ref).max()))
+
+
+# ------------------------------------------------------------------ the rule against float64 torch
+@pytest.mark.parametrize('res,relu', [(0, 0), (1, 1), (0, 1)])
+def test_rule_matches_torch_batchnorm_float64(res, relu):
+    inp = R.bn_input(257, 32, seed=1)
+    bn = torch.nn.BatchNorm1d(32, eps=R.EPS, momentum=float(np.float32(R.MOMENTUM))).double()
+    with torch.no_grad():
+        bn.weight.copy_(T(inp['gamma'])); bn.bias.copy_(T(inp['beta']))
+        bn.running_mean.copy_(T(inp['rm0'])); bn.running_var.copy_(T(inp['rv0']))
+    bn.eps = float(np.float32(R.EPS))
+    x, r = T(inp['x']).requires_grad_(True), T(inp['res']).requires_grad_(True)
+    pre = bn(x) + (r if res else 0)
+    y = torch.relu(pre) if relu else pre
+    (y * T(inp['dy'])).sum().backward()
+    fwd = R.bn_forward(inp['x'], inp['gamma'], inp['beta'], inp['res'] if res else None, relu, (inp['rm0'], inp['rv0']))
+    mask = (fwd['pre'] > 0).astype(np.float64) if relu else None
+    assert not relu or np.array_equal(fwd['pre'] > 0, pre.detach().numpy() > 0)          # (no element on the edge)
+    bwd = R.bn_backward(inp['x'], inp['gamma'], fwd, inp['dy'], mask)
+    close(fwd['y'], y.detach().numpy(), 'y')
+    close(fwd['running_mean'], bn.running_mean.numpy(), 'running_mean')
+    close(fwd['running_var'], bn.running_var.numpy(), 'running_var')
+    close(bwd['dx'], x.grad.numpy(), 'dx')
+    close(bwd['dgamma'], bn.weight.grad.numpy(), 'dgamma', rel=1e-9 * 257)       # (relative to the sum of magnitudes, roughly)
+    close(bwd['dbeta'], bn.bias.grad.numpy(), 'dbeta', rel=1e-9 * 257)
+    if res:
+        close(bwd['dres'], r.grad.numpy(), 'dres')
+
+
+def test_rule_matches_torch_eval_and_pair_float64():
+    inp = R.eval_input(9, 32, seed=2)
+    bn = torch.nn.BatchNorm1d(32).double().eval()
+    bn.eps = float(np.float32(R.EPS))
+    with torch.no_grad():
+        bn.weight.copy_(T(inp['gamma'])); bn.bias.copy_(T(inp['beta']))
+        bn.running_mean.copy_(T(inp['rm0'])); bn.running_var.copy_(T(inp['rv0']))
+    x = T(inp['x']).requires_grad_(True)
+    y = torch.relu(bn(x))
+    (y * T(inp['dy'])).sum().backward()
+    fwd = R.bn_eval_forward(inp['x'], inp['gamma'], inp['beta'], inp['rm0'], inp['rv0'], None, True)
+    bwd = R.bn_eval_backward(inp['x'], fwd, inp['dy'], (fwd['pre'] > 0).astype(np.float64))
+    close(fwd['y'], y.detach().numpy(), 'y')
+    close(bwd['dx'], x.grad.numpy(), 'dx')
+    close(bwd['dgamma'], bn.weight.grad.numpy(), 'dgamma', rel=1e-8)
+    close(bwd['dbeta'], bn.bias.grad.numpy(), 'dbeta', rel=1e-8)
+    assert np.array_equal(T(inp['rm0']).numpy(), bn.running_mean.numpy())                # eval mode leaves them alone
+    # the pair: relu(BN_a(xa) + BN_b(xb)) is the rule of one BatchNorm with the other's output as its residual
+    a, b = R.pair_case_input('pair-n300-c64')
+    fb = R.bn_forward(b['x'], b['gamma'], b['beta'])
+    fa = R.bn_forward(a['x'], a['gamma'], a['beta'], fb['y'], True)
+    bna, bnb = torch.nn.BatchNorm1d(64).double(), torch.nn.BatchNorm1d(64).double()
+    for m, s in ((bna, a), (bnb, b)):
+        m.eps = float(np.float32(R.EPS))
+        with torch.no_grad():
+            m.weight.copy_(T(s['gamma'])); m.bias.copy_(T(s['beta']))
+    xa, xb = T(a['x']).requires_grad_(True), T(b['x']).requires_grad_(True)
+    y = torch.relu(bna(xa) + bnb(xb))
+    (y * T(a['dy'])).sum().backward()
+    close(fa['y'], y.detach().numpy(), 'pair y')
+    mask = (fa['pre'] > 0).astype(np.float64)
+    close(R.bn_backward(a['x'], a['gamma'], fa, a['dy'], mask)['dx'], xa.grad.numpy(), 'pair dx_a')
+    close(R.bn_backward(b['x'], b['gamma'], fb, a['dy'], mask)['dx'], xb.grad.numpy(), 'pair dx_b')
+
+
+@pytest.mark.parametrize('mode', ['avg', 'max'])
+def test_rule_matches_scatter_reduce_float64_without_ties(mode):
+    case = R.seg_case('seg-n7000-c13-random-s211')
+    assert int(np.bincount(case['ids'], minlength=211).min()) > 0
+    x = T(case['x']).requires_grad_(True)
+    idx = torch.from_numpy(case['ids']).reshape(-1, 1).expand(-1, 13)
+    out = torch.zeros(211, 13, dtype=torch.float64).scatter_reduce(0, idx, x, 'mean' if mode == 'avg' else 'amax', include_self=False)
+    (out * T(case['dout'])).sum().backward()
+    ref = R.seg_rule(case['x'], case['ids'], 211, mode, case['dout'])
+    close(ref['out'], out.detach().numpy(), 'out', rel=1e-13)
+    close(ref['dx'], x.grad.numpy(), 'dx', rel=1e-13)
+
+
+# ------------------------------------------------------------------ the conventions, by hand
+def test_conventions_by_hand():
+    x = np.array([[1.0, -2.0], [3.0, -2.0], [3.0, -5.0], [0.0, 0.0], [0.0, -1.0]], dtype=np.float32)
+    ids = np.array([2, 2, 2, 0, 0])
+    dout = np.array([[10.0, 20.0], [30.0, 40.0], [50.0, 60.0], [70.0, 80.0]], dtype=np.float32)
+    mx = R.seg_rule(x, ids, 4, 'max', dout)
+    # segment 2: column 0 has its maximum 3 in rows 1 and 2 -> row 1; column 1 has -2 in rows 0 and 1 -> row 0 (all negative)
+    assert mx['out'].tolist() == [[0.0, 0.0], [0.0, 0.0], [3.0, -2.0], [0.0, 0.0]]
+    assert mx['argmax'].tolist() == [[3, 3], [-1, -1], [1, 0], [-1, -1]]                  # empty segments 1 and 3: 0 and -1
+    assert mx['dx'].tolist() == [[0.0, 60.0], [50.0, 0.0], [0.0, 0.0], [10.0, 20.0], [0.0, 0.0]]
+    assert mx['counts'].tolist() == [2, 0, 3, 0]
+    av = R.seg_rule(x, ids, 4, 'avg', dout)
+    assert av['out'].tolist() == [[0.0, -0.5], [0.0, 0.0], [7.0 / 3.0, -3.0], [0.0, 0.0]]
+    assert av['dx'][0].tolist() == [50.0 / 3.0, 20.0] and av['dx'][3].tolist() == [5.0, 10.0]
+    # a whole segment of post-ReLU zeros: the value 0 is a real maximum, its gradient goes to the first row
+    z = R.seg_rule(np.zeros((3, 1), dtype=np.float32), np.array([1, 1, 1]), 2, 'max', np.array([[5.0], [7.0]], dtype=np.float32))
+    assert z['out'].tolist() == [[0.0], [0.0]] and z['argmax'].tolist() == [[-1], [0]] and z['dx'].tolist() == [[7.0], [0.0], [0.0]]
+    # no rows at all
+    e = R.seg_rule(np.zeros((0, 2), dtype=np.float32), np.zeros(0, dtype=np.int64), 3, 'max', np.ones((3, 2), dtype=np.float32))
+    assert e['out'].tolist() == [[0.0, 0.0]] * 3 and e['dx'].shape == (0, 2) and e['counts'].tolist() == [0, 0, 0]
+    # BatchNorm of two rows: mean 2, biased variance 1, the running variance takes the unbiased 2
+    f = R.bn_forward(np.array([[1.0], [3.0]]), [2.0], [0.5], None, True, ([0.0], [1.0]), eps=0.0, momentum=0.5)
+    assert f['mean'][0] == 2.0 and f['var'][0] == 1.0 and f['y'].tolist() == [[0.0], [2.5]]
+    assert f['running_mean'][0] == 1.0 and f['running_var'][0] == 1.5
+    b = R.bn_backward(np.array([[1.0], [3.0]]), [2.0], f, np.array([[1.0], [1.0]]), (f['pre'] > 0).astype(np.float64))
+    assert b['dbeta'][0] == 1.0 and b['dgamma'][0] == 1.0 and b['dres'].tolist() == [[0.0], [1.0]]
+    assert np.array_equal(R.relu_rule([-1.0, 0.0, 2.0]), np.float32([0, 0, 2]))
+    assert np.array_equal(R.relu_bwd_rule([5.0, 6.0, 7.0], [0.0, 1.0, 0.0]), np.float32([0, 6, 0]))
+    assert np.array_equal(R.add_rule([1.0, 2.0 ** -24], [2.0 ** -24, 1.0]), np.float32([1, 1]))
+
+
+# ------------------------------------------------------------------ the bounds are not too tight
+@functools.lru_cache(maxsize=4)
+def _inp(name):
+    return R.bn_case_input(name)
+
+
+@pytest.mark.parametrize('name', sorted(R.BN_CASES))
+def test_fp32_evaluation_in_another_order_passes_and_few_elements_are_borderline(name):
+    spec, inp = R.BN_CASES[name], _inp(name)
+    n, c = inp['x'].shape
+    assert (n, c) == (spec['n'], spec['c'])
+    kinds = {R.kind_of(j) for j in range(c)}
+    assert kinds == set(R.KINDS[:min(c, 8)])                                              # every case mixes the conditionings
+    if not spec.get('eval') and n >= 255:                                                 # ... and the columns are what they claim
+        m, v = R.bn_stats(inp['x'])
+        for j in range(min(c, 8)):
+            k, sd = R.kind_of(j), np.sqrt(v[j])
+            if k in ('ratio30', 'ratio100', 'ratio1000'):
+                assert 0.8 * float(k[5:]) < abs(m[j]) / sd < 1.25 * float(k[5:]), (k, m[j], sd)
+            elif k in ('ratio0', 'ratio0.5'):                                             # (a sample of n rows: +- 1 / sqrt(n))
+                assert abs(abs(m[j]) / sd - float(k[5:])) < 0.25, (k, m[j], sd)
+            elif k == 'const':
+                assert v[j] == 0.0
+            elif k == 'sigma1e-4':
+                assert v[j] < R.EPS * 1e-2
+            elif k == 'sigma1e4':
+                assert v[j] > 0.5e8
+    got = R.bn_emulate(inp, spec)
+    bad, share = R.bn_check(name, inp, spec, got)
+    assert not bad, (name, bad)
+    assert share <= 1e-3, (name, share)
+
+
+@pytest.mark.parametrize('name', sorted(R.PAIR_CASES))
+def test_pair_fp32_evaluation_passes(name):
+    a, b = R.pair_case_input(name)
+    relu = R.PAIR_CASES[name][2]
+    bad, share = R.pair_check(name, a, b, relu, R.pair_emulate(a, b, relu))
+    assert not bad, (name, bad)
+    assert share <= 1e-3, (name, share)
+
+
+FLAVOURS = {'avg': ('plain',), 'max': ('plain', 'negative', 'ties')}
+
+
+@pytest.mark.parametrize('name', sorted(R.SEG_CASES))
+def test_segment_fp32_evaluation_passes(name):
+    for mode, flavours in FLAVOURS.items():
+        for fl in flavours:
+            case = R.seg_case(name, fl)
+            assert case['x'].shape == (case['n'], case['c']) and (case['n'] == 0 or int(case['ids'].max()) < case['n_seg'])
+            assert not np.any(np.signbit(case['x']) & (case['x'] == 0)) and np.all(np.isfinite(case['x']))
+            bad = R.seg_check('%s %s %s' % (name, mode, fl), case, mode, R.seg_emulate(case, mode), quiet=True)
+            assert not bad, (name, mode, fl, bad)
+
+
+def test_segment_cases_hold_their_edges():
+    ties = R.seg_case('seg-n7000-c96-runs-s120', 'ties')
+    ref = R.seg_rule(ties['x'], ties['ids'], 120, 'max')
+    hit = (ties['x'] == ref['out'][ties['ids']]).astype(np.int64)
+    per = np.zeros((120, 96), dtype=np.int64)
+    np.add.at(per, ties['ids'], hit)
+    assert int((per > 1).sum()) > 1000                                                    # equal maxima, many of them
+    zero_seg = [s for s in np.unique(ties['ids']) if not ties['x'][ties['ids'] == s].any()]
+    assert len(zero_seg) >= 3 and all(bool((ref['argmax'][s] == np.nonzero(ties['ids'] == s)[0][0]).all()) for s in zero_seg)
+    neg = R.seg_case('seg-n7000-c96-runs-s120', 'negative')
+    assert float(neg['x'].max()) < 0 and float(R.seg_rule(neg['x'], neg['ids'], 120, 'max')['out'].min()) < 0
+    runs = R.seg_case('seg-n7000-c96-runs-s120')
+    change = np.nonzero(np.diff(runs['ids']))[0] + 1
+    assert len(change) > 20 and np.any(change % 64 != 0) and int(np.diff(change).max()) > 64  # runs cross the 64-row blocks
+    assert int((np.bincount(runs['ids'], minlength=120) == 0).sum()) > 0                  # and leave segments empty
+    gaps = R.seg_case('seg-n7000-c3-gaps-s50')
+    assert int((np.bincount(gaps['ids'], minlength=50) == 0).sum()) >= 30
+    many = R.seg_case('seg-n63-c96-random-s200')
+    assert many['n_seg'] > many['n']
+    assert R.seg_case('seg-n0-c96-random-s5')['x'].shape == (0, 96) and R.seg_case('seg-n0-c13-random-s0')['n_seg'] == 0
+
+
+# ------------------------------------------------------------------ the bounds are not too loose
+LOOSE_ON = ('small-n257-c96-res1-relu1', 'stats-n257-c96-res1-relu1-ldc+4', 'stats-n2-c4-res1-relu1', 'small-n2-c4-res1-relu1',
+            'stats-n5000-c256-res1-relu1', 'sync-n257-c32-res0-relu1')
+
+
+@pytest.mark.parametrize('mistake', [m for m in R.MISTAKES if m != 'fp32_chains'])
+def test_a_deliberate_mistake_fails(mistake):
+    failed = []
+    for name in LOOSE_ON:
+        assert name in R.BN_CASES, name
+        bad, _ = R.bn_check(name, _inp(name), R.BN_CASES[name], R.bn_emulate(_inp(name), R.BN_CASES[name], mistake), quiet=True)
+        if bad:
+            failed.append((name, bad))
+    print(mistake, failed)
+    assert failed, 'the bounds let the mistake %s pass on every case' % mistake
+
+
+@pytest.mark.parametrize('name', ['stats-n20000-c96-res1-relu1', 'stats-n5000-c256-res1-relu1'])
+def test_fp32_accumulation_of_the_statistics_fails_the_constants(name):
+    """What bn_stats_kernel did before it accumulated in fp64: fp32 chains (here of 25 rows) of sum x and sum x^2.  invstd must
+    miss its bound on the columns with |mean| = 30, 100 and 1000 sigma -- and pass where the mean is small."""
+    spec, inp = R.BN_CASES[name], _inp(name)
+    got = R.bn_emulate(inp, spec, 'fp32_chains')
+    fwd = R.bn_forward(inp['x'], inp['gamma'], inp['beta'], None, False, (inp['rm0'], inp['rv0']))
+    cb = R.const_bounds(inp['x'], inp['gamma'], fwd)
+    r = np.abs(got['invstd'].astype(np.float64) - fwd['invstd']) / cb['invstd']
+    kinds = np.array([R.kind_of(j) for j in range(spec['c'])])
+    for k in ('ratio30', 'ratio100', 'ratio1000'):
+        print(name, k, 'invstd error / bound: max %.1f, columns over %d of %d' % (r[kinds == k].max(), (r[kinds == k] > 1).sum(),
+                                                                                 (kinds == k).sum()))
+        assert r[kinds == k].max() > 1.0, (k, r[kinds == k])
+    assert r[kinds == 'ratio1000'].min() > 10.0
+    assert r[(kinds == 'ratio0') | (kinds == 'ratio0.5')].max() <= 1.0
+
+
+@pytest.mark.parametrize('mistake', R.SEG_MISTAKES)
+def test_a_deliberate_pooling_mistake_fails(mistake):
+    failed = []
+    for name in ('seg-n65-c96-runs-s4', 'seg-n65-c1-gaps-s12', 'seg-n7000-c96-runs-s120'):
+        for mode, fl in (('avg', 'plain'), ('max', 'ties')):
+            case = R.seg_case(name, fl)
+            if R.seg_check(name, case, mode, R.seg_emulate(case, mode, mistake), quiet=True):
+                failed.append((name, mode))
+    assert failed, mistake
+    if mistake == 'highest_tie':
+        assert all(m == 'max' for _, m in failed)
+
+
+def test_oracle_max_pool_follows_the_rule_on_ties():
+    """oracle/sparse_ref.segment_pool('max') gives the gradient to the lowest tied row, like the kernel and the rule."""
+    from oracle import sparse_ref as S
+    for name, fl in (('seg-n7000-c96-runs-s120', 'ties'), ('seg-n65-c1-gaps-s12', 'ties'), ('seg-n63-c96-random-s200', 'negative'),
+                     ('seg-n0-c96-random-s5', 'plain')):
+        c = R.seg_case(name, fl)
+        x = torch.from_numpy(c['x']).requires_grad_(True)
+        o = S.segment_pool(x, torch.from_numpy(c['ids']), c['n_seg'], 'max')
+        (o * torch.from_numpy(c['dout'])).sum().backward()
+        ref = R.seg_rule(c['x'], c['ids'], c['n_seg'], 'max', c['dout'])
+        assert np.array_equal(o.detach().numpy(), ref['out']) and np.array_equal(x.grad.numpy(), ref['dx']), (name, fl)
