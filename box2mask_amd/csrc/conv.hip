@@ -923,22 +923,24 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
     hipStream_t st = (hipStream_t)stream;
     if (wrote_stats) *wrote_stats = 0;
     if (fused) *fused = 0;
-    B2M_CHECK_ARG(x1 && wp && y && c1 > 0 && c2 >= 0 && cout > 0 && K >= 1 && K <= 128, "bad pointers/sizes (K<=128)");
-    B2M_CHECK_ARG((rb_in == nullptr) == (rb_out == nullptr) && (rb_in == nullptr) == (rb_cnt == nullptr),
-                  "rulebook pointers must be all set or all NULL");
-    B2M_CHECK_ARG(rb_in != nullptr || K == 1, "identity rulebook needs K == 1");
-    B2M_CHECK_ARG(c2 == 0 || x2 != nullptr, "x2 is NULL");
-    B2M_CHECK_ARG(n_in >= 1, "n_in (rows of x1/x2) must be >= 1");
+    // the scalar arguments first: an empty output returns behind them, whatever the pointers of its (empty) tensors are
+    B2M_CHECK_ARG(c1 > 0 && c2 >= 0 && cout > 0 && K >= 1 && K <= 128 && n_in >= 0 && n_out >= 0, "bad sizes (K<=128)");
     B2M_CHECK_ARG(ldy >= cout && ldx1 >= c1 && (c2 == 0 || ldx2 >= c2), "leading dimension too small");
-    B2M_CHECK_ARG(((uintptr_t)wp % 16) == 0, "packed weights must be 16-byte aligned");
     const int cin = c1 + c2;
     const int KC = conv_kc(cin);
     const int KS = KC / 4;
     B2M_CHECK_ARG(c2 == 0 || c1 % KC == 0, "with two sources c1 must be a multiple of 16");
+    if (n_out == 0) return B2M_OK;
+    B2M_CHECK_ARG(n_in >= 1, "n_in (rows of x1/x2) must be >= 1 where there are output rows");
+    B2M_CHECK_ARG(x1 && wp && y, "bad pointers");
+    B2M_CHECK_ARG((rb_in == nullptr) == (rb_out == nullptr) && (rb_in == nullptr) == (rb_cnt == nullptr),
+                  "rulebook pointers must be all set or all NULL");
+    B2M_CHECK_ARG(rb_in != nullptr || K == 1, "identity rulebook needs K == 1");
+    B2M_CHECK_ARG(c2 == 0 || x2 != nullptr, "x2 is NULL");
+    B2M_CHECK_ARG(((uintptr_t)wp % 16) == 0, "packed weights must be 16-byte aligned");
     // fast path: every chunk is complete and every gathered segment is aligned; otherwise per-element loads
     const bool fast = c1 % KC == 0 && c2 % KC == 0 && ldx1 % KS == 0 && (c2 == 0 || ldx2 % KS == 0) &&
                       ((uintptr_t)x1 % (4 * KS)) == 0 && ((uintptr_t)x2 % (4 * KS)) == 0;
-    if (n_out == 0) return B2M_OK;
     ConvArgs a{};
     a.x1 = x1; a.ldx1 = ldx1; a.c1 = c1; a.x2 = x2; a.ldx2 = ldx2; a.c2 = c2;
     a.wp = wp; a.K = K; a.bias = bias;
@@ -1181,11 +1183,13 @@ extern "C" int b2m_conv_up(const float* x1, int64_t ldx1, int32_t c1, const floa
     hipStream_t st = (hipStream_t)stream;
     B2M_CHECK_ARG(ran, "ran is NULL");
     *ran = 0;
-    B2M_CHECK_ARG(x1 && wp && y && rb_in && rb_out && rb_cnt && c1 > 0 && c2 >= 0 && cout > 0 && K >= 1 && K <= 128, "bad pointers/sizes");
-    B2M_CHECK_ARG(c2 == 0 || x2 != nullptr, "x2 is NULL");
+    // (scalar arguments first, then an empty map returns: conv_fwd_impl)
+    B2M_CHECK_ARG(c1 > 0 && c2 >= 0 && cout > 0 && K >= 1 && K <= 128 && n_coarse >= 0 && n_fine >= 0, "bad sizes");
     B2M_CHECK_ARG(ldy >= cout && ldx1 >= c1 && (c2 == 0 || ldx2 >= c2), "leading dimension too small");
     B2M_CHECK_ARG((scale == nullptr) == (shift == nullptr), "scale and shift come together");
-    if (n_coarse <= 0 || n_fine <= 0) { *ran = 1; return B2M_OK; }
+    if (n_coarse == 0 || n_fine == 0) { *ran = 1; return B2M_OK; }
+    B2M_CHECK_ARG(x1 && wp && y && rb_in && rb_out && rb_cnt, "bad pointers");
+    B2M_CHECK_ARG(c2 == 0 || x2 != nullptr, "x2 is NULL");
     const int cin = c1 + c2;
     const int TW = conv_tw(cout, K);
     ConvArgs a{};
@@ -1392,17 +1396,19 @@ static int conv_fwd_h_impl(const void* x1, int64_t ldx1, int32_t c1, const void*
                            int64_t n_out, void* y, int64_t ldy, int32_t cout, const float* scale, const float* shift,
                            const void* res, int64_t ld_res, int32_t relu, double* tile_stats, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(x1 && wp && y && rb_in && rb_out && rb_cnt && c1 > 0 && c2 >= 0 && cout > 0 && K >= 1 && K <= 128, "bad pointers/sizes (K<=128)");
+    // (scalar arguments first, then an empty output returns: conv_fwd_impl)
+    B2M_CHECK_ARG(c1 > 0 && c2 >= 0 && cout > 0 && K >= 1 && K <= 128 && n_in >= 0 && n_out >= 0, "bad sizes (K<=128)");
+    B2M_CHECK_ARG(c1 % 16 == 0 && c2 % 16 == 0 && cout % 16 == 0, "channels must be multiples of 16");
+    if (n_out == 0) return B2M_OK;
+    B2M_CHECK_ARG(x1 && wp && y && rb_in && rb_out && rb_cnt, "bad pointers");
     B2M_CHECK_ARG(c2 == 0 || x2 != nullptr, "x2 is NULL");
     B2M_CHECK_ARG((scale == nullptr) == (shift == nullptr), "scale and shift: both or none");
-    B2M_CHECK_ARG(c1 % 16 == 0 && c2 % 16 == 0 && cout % 16 == 0, "channels must be multiples of 16");
     B2M_CHECK_ARG(ldx1 % 8 == 0 && ldx1 >= c1 && (c2 == 0 || (ldx2 % 8 == 0 && ldx2 >= c2)) && ldy % 4 == 0 && ldy >= cout &&
                   (!res || (ld_res % 4 == 0 && ld_res >= cout)), "row pitches: 16-byte multiples for the inputs, 8 for output / residual");
     B2M_CHECK_ARG(((uintptr_t)x1 % 16) == 0 && ((uintptr_t)x2 % 16) == 0 && ((uintptr_t)wp % 16) == 0 && ((uintptr_t)y % 8) == 0 &&
                   ((uintptr_t)res % 8) == 0 && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)shift % 16) == 0, "alignment");
     B2M_CHECK_ARG(n_in >= 1 && n_in < (1 << 24) && ldx1 < (1 << 22) && ldx2 < (1 << 22) && n_in * ldx1 * 2 < (1ll << 32) &&
-                  n_in * ldx2 * 2 < (1ll << 32), "inputs must be 32-bit addressable (rows < 2^24, tensors < 4 GiB)");
-    if (n_out == 0) return B2M_OK;
+                  n_in * ldx2 * 2 < (1ll << 32), "inputs must be 32-bit addressable (1 <= rows < 2^24, tensors < 4 GiB)");
     ConvArgs a{};
     a.x1 = (const float*)x1; a.ldx1 = ldx1; a.c1 = c1; a.x2 = (const float*)x2; a.ldx2 = ldx2; a.c2 = c2;
     a.wp = (const float*)wp; a.K = K; a.bias = nullptr;
@@ -2511,14 +2517,17 @@ static int conv_wgrad_impl(const float* x, int64_t ldx, int32_t cin, int64_t n_i
                            int64_t n_out, int32_t K, float* dw, int64_t lddw, int64_t dw_kstride, float* workspace,
                            void* stream, int tr, int half, float out_scale) {
     hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(x && dy && dw && cin > 0 && cout > 0 && K >= 1 && K <= 65535 && n_in >= 0, "bad pointers/sizes");
+    // (scalar arguments first; without input or output rows there are no pairs and dW stays as it is, whatever the pointers of the
+    // empty tensors are)
+    B2M_CHECK_ARG(cin > 0 && cout > 0 && K >= 1 && K <= 65535 && n_in >= 0 && n_out >= 0, "bad sizes");
+    B2M_CHECK_ARG(ldx >= cin && lddy >= cout && lddw >= cout && dw_kstride >= (int64_t)cin * lddw,
+                  "leading dimension too small");
+    if (n_out == 0 || n_in == 0) return B2M_OK;
+    B2M_CHECK_ARG(x && dy && dw, "bad pointers");
     B2M_CHECK_ARG((rb_in == nullptr) == (rb_out == nullptr) && (rb_in == nullptr) == (rb_cnt == nullptr),
                   "rulebook pointers must be all set or all NULL");
     B2M_CHECK_ARG(rb_in != nullptr || K == 1, "identity rulebook needs K == 1");
     B2M_CHECK_ARG(!tr || rb_in != nullptr, "b2m_conv_wgrad_tr needs a rulebook");
-    B2M_CHECK_ARG(ldx >= cin && lddy >= cout && lddw >= cout && dw_kstride >= (int64_t)cin * lddw,
-                  "leading dimension too small");
-    if (n_out == 0) return B2M_OK;
     WgradArgs a{};
     a.swap = tr;
     a.half = half;

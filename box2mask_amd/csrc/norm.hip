@@ -391,12 +391,33 @@ static unsigned ew_grid(int64_t total) {
     if (g < 1) g = 1;
     return (unsigned)g;
 }
+// The same map one element per thread, for a channel count or a row pitch that is no multiple of 4 (the inference form of a layer
+// whose kernel cannot take the epilogue and whose width has no 16-byte column groups: functional.conv_affine with cout = 3, 13).
+// Same arithmetic in the same order -- fmaf, + residual, ReLU -- so the bits equal the vector kernel's.  y may be x.
+__global__ __launch_bounds__(256) void bn_apply_elem_kernel(const float* x, int64_t ldx, int64_t n, int c, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, const float* res, int64_t ldr, int relu,
+                                                            float* y, int64_t ldy) {
+    const int64_t total = n * c;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / c;
+        const int col = (int)(i - r * c);
+        float v = __builtin_fmaf(x[r * ldx + col], scale[col], shift[col]);
+        if (res) v += res[r * ldr + col];
+        if (relu) v = v > 0.f ? v : 0.f;
+        y[r * ldy + col] = v;
+    }
+}
 extern "C" int b2m_bn_apply(const float* x, int64_t ldx, int64_t n, int32_t c, const float* scale, const float* shift,
                             const float* residual, int64_t ldr, int32_t relu, float* y, int64_t ldy, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(x && y && scale && shift && c > 0 && c % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 &&
-                      (!residual || ldr % 4 == 0),
-                  "c and leading dimensions must be multiples of 4");
+    B2M_CHECK_ARG(x && y && scale && shift && c > 0 && n >= 0, "bad pointers/sizes");
+    if (c % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || (residual && ldr % 4 != 0)) {
+        B2M_CHECK_ARG(ldx >= c && ldy >= c && (!residual || ldr >= c), "leading dimension too small");
+        if (n == 0) return B2M_OK;
+        bn_apply_elem_kernel<<<ew_grid(n * c), 256, 0, st>>>(x, ldx, n, c, scale, shift, residual, ldr, relu, y, ldy);
+        B2M_LAUNCH_CHECK();
+        return B2M_OK;
+    }
     if (n == 0) return B2M_OK;
     B2M_CHECK_ARG(c <= 1024, "c <= 1024");
     bn_apply_kernel<<<row_grid(n, c / 4), 256, 0, st>>>(x, ldx, n, c / 4, scale, shift, residual, ldr, relu, y, ldy);

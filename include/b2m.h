@@ -187,7 +187,11 @@ int b2m_weight_pack_run(const void* plan_dev, int32_t n, int64_t total_blocks, v
  *   accumulate != 0: add to the existing Y instead of overwriting
  * The same entry computes the data gradient when given the transposed/mirrored image.
  * Maps with fewer than 4096 (tile, 32-channel strip) items split the kernel offsets over several waves
- * that combine with fp32 atomics (sum order then varies in the last bits). */
+ * that combine with fp32 atomics (sum order then varies in the last bits).
+ * Empty maps, for this entry and for b2m_conv_fwd_affine / _stats / _h / _h_stats, b2m_conv_up and b2m_conv_wgrad / _tr / _h alike:
+ * the scalar arguments (channel counts, K, row pitches) are checked first; n_out == 0 is allowed, nothing is written and the
+ * tensors' pointers may be NULL, with n_in == 0 as well.  The weight gradients also return on n_in == 0 (no pairs: dW stays as it
+ * is).  The forward entries REFUSE n_out > 0 with n_in == 0 (B2M_ERR_ARG): their kernels are given a row to read. */
 int b2m_conv_fwd(const float* x1, int64_t ldx1, int32_t c1, const float* x2, int64_t ldx2, int32_t c2,
                  int64_t n_in, const float* wp, int32_t K, const float* bias,
                  const int32_t* rb_in, const uint8_t* rb_out, const int32_t* rb_cnt,
@@ -399,7 +403,10 @@ int b2m_bn_finalize(const double* stats, double count, const double* count_dev, 
                     float eps, float momentum, float* running_mean, float* running_var,
                     float* mean, float* invstd, float* scale, float* shift, void* stream);
 
-/* y = x*scale + shift (+ residual) (ReLU if relu) */
+/* y = x*scale + shift (+ residual) (ReLU if relu).  c and the row pitches multiples of 4: 16-byte column groups; anything else:
+ * one element per thread, the same bits (for functional.conv_affine on widths like 3 and 13; an eval-mode BatchNorm
+ * forward of such a width passes with it; the statistics and backward entries still need c % 4 == 0, so training mode is refused
+ * as before, by them). */
 int b2m_bn_apply(const float* x, int64_t ldx, int64_t n, int32_t c, const float* scale, const float* shift,
                  const float* residual, int64_t ldr, int32_t relu, float* y, int64_t ldy, void* stream);
 

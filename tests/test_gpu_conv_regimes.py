@@ -20,6 +20,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _dense import random_sites as _random_sites, dense_weight as _dense_weight, scatter_dense as _scatter_dense, read_dense as _read_dense
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-3        # north_star: conv features within 1e-3 fp32
 
@@ -203,33 +205,6 @@ def test_full_size_layer_1p2m_rows():
 
 
 # ------------------------------------------------------------------ 3. dense equivalence, random occupancy, no oracle
-def _random_sites(B, X, Y, Z, density, seed):
-    rng = np.random.default_rng(seed)
-    occ = rng.random((B, X, Y, Z)) < density
-    occ[:, 0, 0, 0] = True                       # pin the grid origin so that dense and sparse indices agree
-    c = np.argwhere(occ).astype(np.int32)
-    return c[rng.permutation(len(c))]            # rows in random order
-
-
-def _dense_weight(w, k):
-    """(K,Cin,Cout), offset index x-fastest -> conv3d weight (Cout,Cin,kx,ky,kz) for a dense [b,c,x,y,z] grid."""
-    K, ci, co = w.shape
-    return w.reshape(k, k, k, ci, co).permute(4, 3, 2, 1, 0).contiguous()
-
-
-def _scatter_dense(feat, coords, shape, ts=1):
-    B, X, Y, Z = shape
-    d = torch.zeros(B, feat.shape[1], X, Y, Z, dtype=feat.dtype)
-    c = torch.as_tensor(coords).long()
-    d[c[:, 0], :, c[:, 1] // ts, c[:, 2] // ts, c[:, 3] // ts] = feat
-    return d
-
-
-def _read_dense(d, coords, ts=1):
-    c = torch.as_tensor(coords).long()
-    return d[c[:, 0], :, c[:, 1] // ts, c[:, 2] // ts, c[:, 3] // ts]
-
-
 @pytest.mark.parametrize('ksize,level,cin,cout', [(3, 0, 32, 48), (3, 0, 96, 96), (5, 0, 6, 32), (3, 1, 64, 64)])
 def test_dense_equivalence_stride1_random_occupancy(ksize, level, cin, cout):
     from box2mask_amd import functional as F_
