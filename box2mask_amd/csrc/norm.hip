@@ -3,7 +3,7 @@
 // Precision contract (tests/_norm_rule.py holds every path to it): the BatchNorm STATISTICS are fp64 sums of the fp32 inputs on
 // every path -- bn_stats_kernel, bn_small_fwd_kernel, the convolution's tile sums -- and the finalize math is fp64, one rounding per
 // fp32 constant.  The BACKWARD sums (sum g, sum g * xhat) go through the skeleton below: fp32 chains of at most 64 terms per
-// thread, fp64 from there on (the one-launch kernels: fp64 throughout).  The binary16 statistics kernel keeps the fp32 chains.
+// thread, fp64 from there on (the one-launch kernels: fp64 throughout).  The binary16 twins: the same, on the widened half inputs.
 #include "b2m_common.h"
 
 #define RED_MAX_BLOCKS 1280   // 256 CUs x 5 resident blocks of bn_bwd_reduce: one full round, no tail (4096: 12 % slower)
@@ -134,12 +134,11 @@ static int reduce_blocks(int64_t n) {
 }
 
 // ------------------------------------------------------------------ BN forward
-// Statistics from x: the skeleton with FP64 accumulators -- every element is widened before it is added, and x * x is exact in a
-// double -- as bn_small_fwd_kernel and the convolution's tile sums do.  The variance is the difference of the two sums: with fp32
+// Statistics from x (here and in bn_stats_h_kernel, the binary16 twin): the skeleton with FP64 accumulators -- every element is
+// widened before it is added, and x * x is exact in a double -- as bn_small_fwd_kernel and the convolution's tile sums do.  The variance is the difference of the two sums: with fp32
 // chains a column whose |mean| is 100 sigma loses about 160 ulps of invstd and one at 1000 sigma 7e-4 relative (SIMULATED in numpy
 // with this launch geometry, not measured on a device; tests/test_norm_rule.py repeats the simulation with chains of 25 rows).  With
 // fp64 sums every path rounds to the fp32 constants of the exact value.  Three fp64 operations per element loaded: HBM-bound.
-// (The binary16 twin and the backward sums keep fp32 chains.)
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int c,
                                                        double* __restrict__ partial) {
     typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -555,9 +554,11 @@ extern "C" int b2m_bn_bwd_apply(const float* dy, int64_t lddy, const float* y, i
 // ------------------------------------------------------------------ half-precision training: BatchNorm with binary16 I/O
 // (round 6; /root/reference/configs/arkitscenes.txt is the workload BASELINE names for it.)  The activations and their gradients live
 // in HBM as IEEE half -- every pass below moves half the bytes of its fp32 twin --; statistics, the per-column constants and
-// all arithmetic stay fp32 / fp64 exactly as above, one rounding to half on the way out.  The ReLU mask is always the stored
-// output's sign (y > 0 on the half value the next layer saw), never recomputed from x: a pre-activation that rounds to +0 must
-// be "off" in both directions.  Pitches in ELEMENTS, multiples of 4; 8-byte aligned rows.
+// all arithmetic stay fp32 / fp64 exactly as above (the statistics: fp64 accumulators, as bn_stats_kernel), one rounding to half
+// on the way out.  The ReLU mask: where a residual is fused, the stored output's sign (y > 0 on the half value the next layer saw);
+// where none is, the sign of the forward's fp32 fmaf(x, scale, shift), recomputed from x (see bn_bwd_reduce_h_kernel: y is not a
+// faithful witness there -- a positive value below 2^-25 stores as 0 and still counts as on).  tests/_norm_rule.py (bn_check_half)
+// holds both.  Pitches in ELEMENTS, multiples of 4; 8-byte aligned rows.
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 ldh4(const _Float16* p) {
     const h16x4 v = *(const h16x4*)p;
@@ -570,9 +571,10 @@ __device__ __forceinline__ void sth4(_Float16* p, const f32x4 v) {
 }
 __global__ __launch_bounds__(256) void bn_stats_h_kernel(const _Float16* __restrict__ x, int64_t ldx, int64_t n, int c,
                                                          double* __restrict__ partial) {
-    column_reduce_staged<1>(n, c, partial,
+    typedef double f64x4 __attribute__((ext_vector_type(4)));
+    column_reduce_staged<1, double>(n, c, partial,
         [&](int64_t r, int cg, f32x4 (&in)[1]) { in[0] = ldh4(x + r * ldx + cg * 4); },
-        [&](const f32x4 (&in)[1], f32x4& a, f32x4& b) { a = in[0]; b = in[0] * in[0]; });
+        [&](const f32x4 (&in)[1], f64x4& a, f64x4& b) { a = __builtin_convertvector(in[0], f64x4); b = a * a; });
 }
 extern "C" int b2m_bn_stats_h(const void* x, int64_t ldx, int64_t n, int32_t c, double* partial, double* stats, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -581,7 +583,7 @@ extern "C" int b2m_bn_stats_h(const void* x, int64_t ldx, int64_t n, int32_t c, 
     B2M_CHECK_ARG(((uintptr_t)x % 8) == 0, "x must be 8-byte aligned");
     const int nblk = reduce_blocks(n);
     const int c4 = c / 4, nslots = 256 / c4;
-    bn_stats_h_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(float), st>>>((const _Float16*)x, ldx, n, c, partial);
+    bn_stats_h_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(double), st>>>((const _Float16*)x, ldx, n, c, partial);
     reduce_final_kernel<<<2 * c, 64, 0, st>>>(partial, nblk, 2 * c, stats, nullptr, nullptr);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
@@ -596,7 +598,7 @@ extern "C" int b2m_bn_stats_finalize_h(const void* x, int64_t ldx, int64_t n, in
     B2M_CHECK_ARG(((uintptr_t)x % 8) == 0, "x must be 8-byte aligned");
     const int nblk = reduce_blocks(n);
     const int c4 = c / 4, nslots = 256 / c4;
-    bn_stats_h_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(float), st>>>((const _Float16*)x, ldx, n, c, partial);
+    bn_stats_h_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(double), st>>>((const _Float16*)x, ldx, n, c, partial);
     bn_final_finalize_kernel<<<c, 64, 0, st>>>(partial, nblk, (double)n, c, gamma, beta, eps, momentum, running_mean, running_var,
                                                mean, invstd, scale, shift, nullptr);
     B2M_LAUNCH_CHECK();

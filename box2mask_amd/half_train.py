@@ -8,9 +8,11 @@ stay fp32, as do the weights (master copies, the optimizer's); every accumulatio
 * forward and data gradient of a layer: `b2m_conv_fwd_h` (conv_fwd_flow_kernel<.., F16>: f16 MFMA, fp32 accumulators, one
   rounding to half on the way out) -- the data gradient with the half image of the transposed (and, for the stride-1 maps,
   mirrored) weights;
-* weight gradient: `b2m_conv_wgrad_h` (half operands converted on load, fp32 MFMA, fp32 dW);
+* weight gradient: `b2m_conv_wgrad_h` (f16 MFMA on complete 16-channel blocks -- the product of two halves is exact in fp32 --, else
+  half operands converted on load and the fp32 MFMA; fp32 dW);
 * BatchNorm: `b2m_bn_stats_finalize_h` -> `b2m_bn_apply_h`, backward `b2m_bn_bwd_reduce_h` -> `b2m_bn_bwd_apply_h`
-  (statistics: fp32 chains of at most 64 rows per thread, fp64 from there on and in the finalize math; the ReLU mask is the sign of the stored half output);
+  (statistics: fp64 sums of the widened inputs and fp64 finalize math, as the fp32 operator; the ReLU mask is the sign of the stored
+  half output where a residual is fused, else the sign of the fp32 fmaf(x, scale, shift) recomputed from x -- y is not kept);
 * loss scaling: the gradient is multiplied by `loss_scale` where it enters the half region (`to_float`), every parameter gradient
   the region produces is multiplied by 1 / loss_scale by the operator that produced it, and the gradient that leaves the region
   towards the stem (`to_half`) likewise -- outside the region nothing is scaled.

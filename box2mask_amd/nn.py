@@ -213,7 +213,7 @@ class MinkowskiBatchNorm(nn.Module):
                 bn.num_batches_tracked.add_(1)
         if training:
             F_.note_training_pass()        # running statistics are about to change behind torch's back (eval_affine)
-        if feats.dtype == torch.float16:   # half-precision training (half_train.py): binary16 in / out; statistics from fp32 chains of <= 64 rows, fp64 beyond (or the convolution's fp64 tile sums)
+        if feats.dtype == torch.float16:   # half-precision training (half_train.py): binary16 in / out; statistics accumulated in fp64 from x (or from the convolution's fp64 tile sums)
             from . import half_train as HT
             if not training:
                 raise RuntimeError('half activations outside inference need training-mode BatchNorm (half_train.py)')

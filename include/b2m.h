@@ -295,13 +295,17 @@ int b2m_conv_wgrad_tr(const float* x, int64_t ldx, int32_t cin, int64_t n_in, co
  *                         multiples of 8 elements) and a real rulebook the products run on the f16 MFMA (operands transposed by
  *                         ds_read_b64_tr_b16; the product of two halves is exact in fp32, the sums differ by their order);
  *                         otherwise the operands are converted on load and multiplied on the fp32 MFMA.
- *   b2m_bn_stats_h        column sums / sums of squares of a half tensor (fp64; partial: 2*c*4096 doubles; stats: 2*c).
+ *   b2m_bn_stats_h        column sums / sums of squares of a half tensor (every element widened to fp64 before it is added;
+ *                         partial: 2*c*4096 doubles; stats: 2*c).
  *   b2m_bn_apply_h        y = [relu](fmaf(x, scale, shift) [+ res]), half in / out.
- *   b2m_bn_bwd_reduce_h   sums[0:c] = sum g, sums[c:2c] = sum g * xhat with g = dy * (y > 0) (relu); dbeta / dgamma = the sums as
- *                         fp32 times param_grad_scale (1 / loss scale).
+ *   b2m_bn_bwd_reduce_h   sums[0:c] = sum g, sums[c:2c] = sum g * xhat with g = dy * mask (relu); dbeta / dgamma = the sums as
+ *                         fp32 times param_grad_scale (1 / loss scale; a power of two is exact, the fp64 sums stay scaled).
  *   b2m_bn_bwd_apply_h    dx = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat)), dres = g; half out.
- * The BatchNorm arithmetic is that of b2m_bn_stats / _apply / _bwd_reduce / _bwd_apply (resnet.py:63,66,73-82); the ReLU mask
- * is always the sign of the stored half output y. */
+ * The BatchNorm arithmetic is that of b2m_bn_stats / _apply / _bwd_reduce / _bwd_apply (resnet.py:63,66,73-82), one rounding to
+ * half (nearest even; IEEE: +-inf from 65520) on the way out.  The ReLU mask: with y given (a fused residual) the sign of the
+ * stored half output; with y == NULL the sign of the forward's fp32 fmaf(x, mask_scale, mask_shift), recomputed from x -- y is no
+ * witness of it (a positive value below 2^-25 stores as 0 and counts as on).  b2m_bn_bwd_apply_h writes the masked gradient to
+ * dres whenever dres is given, whatever the forward fused.  tests/test_gpu_norm_half.py holds all of it to the fp64 rule. */
 int b2m_conv_wgrad_h(const void* x, int64_t ldx, int32_t cin, int64_t n_in, const void* dy, int64_t lddy, int32_t cout,
                      const int32_t* rb_in, const uint8_t* rb_out, const int32_t* rb_cnt, int64_t n_out, int32_t K,
                      float* dw, int64_t lddw, int64_t dw_kstride, int32_t tr, float out_scale, void* stream);

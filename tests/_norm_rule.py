@@ -3,7 +3,8 @@ fused residual add and ReLU (the reference's models/resnet.py:61-83: MinkowskiBa
 `out += residual; relu`), the pair of BatchNorms that meet in one add (resnet.py:73-82), segment mean / max pooling
 (models/detection_net.py:345-352: global pooling by pooling id), ReLU and add -- together with the error bounds the kernels are
 held to and the seeded cases shared by tests/test_norm_rule.py (CPU: the rule against float64 torch, the bounds against an fp32
-evaluation in another order and against deliberate mistakes) and tests/test_gpu_norm.py (the kernels against the rule).
+evaluation in another order and against deliberate mistakes) and tests/test_gpu_norm.py (the kernels against the rule).  The last
+section holds the binary16 BatchNorm kernels and the grouped SyncBN operator to the same rule (tests/test_gpu_norm_half.py).
 
 Everything is numpy float64 on the fp32 inputs widened exactly; column statistics are two-pass (mean, then the mean of the
 squared deviations).  Inputs contain no -0.0, no NaN and no infinity: the packed atomic max of the kernel orders -0.0 below
@@ -162,9 +163,15 @@ def grad_bounds(x, gamma, fwd, bwd, chain, any_order=False):
     of the four magnitudes |g|, |gbar|, |xhat gxbar| and (through xh's mean) |mean| invstd |gxbar|, all scaled by |gamma invstd|,
     plus the two sums' own errors carried through:
         |d dx| <= |gamma invstd| (8 u (|g| + |gbar| + |xhat gxbar| + |mean| invstd |gxbar|) + B_dbeta / n + |xhat| B_dgamma / n)
-    any_order (the eval-mode gradients are torch reductions whose order is not ours to know): L = n."""
+    any_order (the eval-mode gradients are torch reductions whose order is not ours to know): L = n.
+    The binary16 entries accept c up to 1024, where a thread's chain is longer than 64 (114 rows at c = 512): their bounds call
+    _grad_bounds with the L that chain_len derives from the launch geometry; the formulas are these."""
+    return _grad_bounds(x, gamma, fwd, bwd, f64(x).shape[0] if any_order else CHAIN[chain])
+
+
+def _grad_bounds(x, gamma, fwd, bwd, L):
+    """grad_bounds for an fp32 chain of L terms (chain_len gives the L of a launch geometry)."""
     n = f64(x).shape[0]
-    L = n if any_order else CHAIN[chain]
     g, xhat = np.abs(bwd['g']), np.abs(bwd['xhat'])
     mi = np.abs(fwd['mean']) * fwd['invstd']
     b_dbeta = (L + 3) * U * g.sum(0)
@@ -674,4 +681,233 @@ def pair_emulate(a, b, relu):
         got.update({'dbeta_' + s: sg, 'dgamma_' + s: sgx,
                     'dx_' + s: (inp['gamma'] * e['invstd']) * (g - sg * inv_n - xh * (sgx * inv_n))})
         got.update({k + '_' + s: e[k] for k in CONSTS})
+    return got
+
+
+# ================================================================== binary16 BatchNorm (half_train._BatchNormH) and grouped SyncBN
+# The half kernels of norm.hip read binary16 x / residual / dy, widen them exactly, do the arithmetic of their fp32 twins and round
+# ONCE to binary16 (round to nearest even) on the way out; gamma, beta, the constants and the running statistics are fp32.  The rule
+# is the fp64 rule above ON THE HALF-ROUNDED INPUTS (exactly what the device reads), and every bound is the fp32 twin's plus what
+# that one rounding can add.  HALF_CASES / GROUP_CASES carry their own seeds: BN_CASES' inputs depend on its sorted key order.
+H_MAX = 65504.0
+H_TINY = 2.0 ** -24                      # the spacing of the binary16 subnormals (and of the first normal binade)
+
+
+def to_half(a):
+    """fp32 -> binary16 (round to nearest even, numpy's conversion; clipped to the largest finite value first) -> fp32, exactly."""
+    return np.clip(np.asarray(a, dtype=np.float32), -H_MAX, H_MAX).astype(np.float16).astype(np.float32)
+
+
+def half_spacing(v):
+    """Distance between neighbouring binary16 values at magnitude |v|: 2^(e - 10) for 2^e <= |v| < 2^(e + 1), e >= -14; the
+    subnormals (|v| < 2^-14) are 2^-24 apart; the top binade (e = 15) reaches 65504 and its spacing, 32, serves above it."""
+    v = np.abs(f64(v))
+    e = np.floor(np.log2(np.maximum(v, 2.0 ** -14)))
+    return 2.0 ** (np.minimum(e, 15.0) - 10.0)
+
+
+def half_store(v32, b):
+    """What one round-to-nearest store to binary16 adds to a bound.  The device holds an fp32 value v with |v - r| <= b (r the
+    rule's, b the fp32 bound) and stores h = half(v): |h - v| <= spacing16(|v|) / 2, and the spacing never decreases with the
+    magnitude, |v| <= |r| + b, so  |h - r| <= b + spacing16(|r| + b) / 2  -- for |r| + b < 65520, where the conversion is finite."""
+    return b + 0.5 * half_spacing(np.abs(f64(v32)) + b)
+
+
+def chain_len(n, c):
+    """Longest fp32 chain of the two-stage skeleton (column_reduce_staged in norm.hip) for n rows of c columns: min(ceil(n / 256),
+    1280) blocks share the rows evenly, a block's rows go round-robin to its 256 / (c / 4) row slots (integer division), and a
+    thread adds its slot's rows in fp32.  <= 64 for c <= 256 and n <= 327 680 (CHAIN['two_stage']); 128 at c = 512, 256 at c = 1024."""
+    nblk = min(max(-(-n // 256), 1), 1280)
+    rows = -(-n // nblk)
+    nslots = 256 // (c // 4)
+    return -(-rows // nslots)
+
+
+def half_input(n, c, seed):
+    inp = bn_input(n, c, seed)
+    for k in ('x', 'res', 'dy'):
+        inp[k] = to_half(inp[k])
+    return inp
+
+
+def _half_cases():
+    cases = {}
+
+    def add(path, n, c, res, relu, ld=None, **kw):
+        name = '%s-n%d-c%d-res%d-relu%d' % (path, n, c, res, relu) + ('-ld%s' % ld if ld else '')
+        cases[name] = dict(path=path, n=n, c=c, res=bool(res), relu=bool(relu), ld=ld, chain=chain_len(n, c), seed=len(cases), **kw)
+    for i, (n, c) in enumerate(((2, 4), (3, 32), (255, 96), (257, 256), (1025, 32))):
+        add('stats_h', n, c, *_V[(i + 3) % 4])
+    for v in _V:
+        add('stats_h', 5000, 96, *v)
+        add('stats_h', 5000, 256, *v)
+    add('stats_h', 2049, 512, 1, 1)
+    add('stats_h', 257, 96, 1, 1, ld='c+4')
+    add('stats_h', 1025, 32, 0, 1, ld='2c')
+    add('stats_h', 1025, 32, 1, 1, ld='2c')
+    add('tiles_h', 65, 32, 1, 1)
+    add('tiles_h', 4097, 96, 0, 1)
+    add('sync_h', 5000, 96, 1, 1, count_factor=2)
+    add('sync_h', 257, 32, 0, 1, count_factor=2, tiles=True)          # (this rank's sums from b2m_bn_tilestats)
+    add('sync_h', 3, 4, 0, 0, count_factor=2)
+    return cases
+
+
+HALF_CASES = _half_cases()
+# members' channel counts; every member is a SyncBN layer without ReLU or residual over the same n rows, the sums doubled
+GROUP_CASES = {'group-n2': (2, (96, 32, 4, 256)), 'group-n257': (257, (96, 32, 4, 256)), 'group-n5000': (5000, (96, 32, 4, 256)),
+               'group-n3-c96x2': (3, (96, 96))}
+GROUP_SPEC = {'relu': False, 'res': False, 'chain': 'two_stage', 'count_factor': 2}
+
+
+def half_case_input(name):
+    s = HALF_CASES[name]
+    return half_input(s['n'], s['c'], 2000 + s['seed'])
+
+
+def group_case_inputs(name):
+    n, cs = GROUP_CASES[name]
+    k = list(GROUP_CASES).index(name)
+    return [bn_input(n, c, 3000 + 10 * k + j) for j, c in enumerate(cs)]
+
+
+def is_pow2(s):
+    m, _ = np.frexp(float(s))
+    return m == 0.5
+
+
+def bn_check_half(tag, inp, spec, got, pgs=1.0, quiet=False):
+    """A binary16 BatchNorm run against the rule.  got: the fp32 constants, y / dx / dres (binary16 values, any float dtype), dbeta /
+    dgamma (fp32, ALREADY multiplied by pgs = param_grad_scale, a float32 value), and -- for ReLU without a residual -- 'mask', the
+    device's own decisions read off the dres the entry writes when asked to.  Returns (failures, borderline share).
+
+    constants  const_bounds as they are: the statistics are fp64 sums of the widened half inputs on every path.
+    y          half_store(y, y_bound): the fp32 value y_bound covers, then one store.
+    dx         half_store(dx, grad_bounds' dx), with the chain length L = spec['chain'] of the launch geometry (chain_len).
+    dres       exact: dy * mask is a binary16 value, widened and stored again.
+    dbeta, dgamma   grad_bounds', times pgs: the kernel forms fl(fl32(S) * pgs).  A power of two only moves the exponent (no
+               underflow at these magnitudes): no new error.  Any other pgs rounds once more: u (|S pgs| + bound) in addition.
+    mask       WITH a fused residual the backward reads the stored y: mask = y16 > 0.  The fp32 value v (|v - pre| <= y_bound) stores
+               as 0 when v <= 2^-25 (tie to even), so the decision may be the device's where |pre| <= y_bound + 2^-24.  WITHOUT one the
+               kernels take the sign of fl(fma(x, scale, shift)) in fp32 and never look at y: borderline where |pre| <= y_bound.
+               Everywhere else the mask must be the rule's pre > 0."""
+    relu, res = spec['relu'], (inp['res'] if spec['res'] else None)
+    cf = spec.get('count_factor', 1)
+    for k in ('x', 'res', 'dy'):
+        assert np.array_equal(to_half(inp[k]), inp[k]), '%s is not binary16' % k
+    fwd = bn_forward(inp['x'], inp['gamma'], inp['beta'], res, relu, (inp['rm0'], inp['rv0']), count_factor=cf)
+    cb = const_bounds(inp['x'], inp['gamma'], fwd, count_factor=cf)
+    yb = y_bound(inp['x'], fwd, res, cb)
+    rows = [(k, got[k], fwd[k], cb[k]) for k in CONSTS if k in got]
+    bad, share, mask = [], 0.0, None
+    if 'y' in got:
+        rows.append(('y', got['y'], fwd['y'], half_store(fwd['y'], yb)))
+    if relu:
+        if spec['res']:
+            mask = f64(got['y']) > 0
+            edge = np.abs(fwd['pre']) <= yb + H_TINY
+        else:
+            mask = np.asarray(got['mask'], dtype=bool)
+            edge = np.abs(fwd['pre']) <= yb
+        share = float(edge.mean())
+        wrong = (mask != (fwd['pre'] > 0)) & ~edge
+        if wrong.any():
+            bad.append('ReLU mask differs in %d elements that are not borderline' % int(wrong.sum()))
+    if 'dx' in got or 'dbeta' in got:
+        m = mask.astype(np.float64) if mask is not None else None
+        bwd = bn_backward(inp['x'], inp['gamma'], fwd, inp['dy'], m)
+        gb = _grad_bounds(inp['x'], inp['gamma'], fwd, bwd, spec['chain'])
+        s = float(np.float32(pgs))
+        for k in ('dbeta', 'dgamma'):
+            if k in got:
+                b = gb[k] * s
+                if not is_pow2(s):
+                    b = b + U * (np.abs(bwd[k]) * s + b)
+                rows.append((k, got[k], bwd[k] * s, b))
+        if 'dx' in got:
+            rows.append(('dx', got['dx'], bwd['dx'], half_store(bwd['dx'], gb['dx'])))
+        if got.get('dres') is not None:
+            rows.append(('dres', got['dres'], bwd['dres'], None))
+    return check(tag, rows, bad, quiet), share
+
+
+def _round_half(v32, toward_zero=False):
+    v32 = np.asarray(v32, dtype=np.float32)
+    h = v32.astype(np.float16)
+    if toward_zero:
+        over = np.abs(h.astype(np.float32)) > np.abs(v32)
+        h = np.where(over, np.nextafter(h, np.float16(0)), h)
+    return h.astype(np.float32)
+
+
+def _chains32(x, c):
+    """Sum x and sum x^2 the way bn_stats_h_kernel formed them while it accumulated in fp32: per block and row slot an fp32 chain in
+    row order (the product of two binary16 values is exact in fp32), the chains added in fp64 (slots, then blocks)."""
+    n = x.shape[0]
+    nblk = min(max(-(-n // 256), 1), 1280)
+    rows = -(-n // nblk)
+    nslots = 256 // (c // 4)
+    s1, s2 = np.zeros(c), np.zeros(c)
+    for b in range(nblk):
+        blk = x[b * rows:min((b + 1) * rows, n)]
+        for rs in range(min(nslots, blk.shape[0])):
+            t = blk[rs::nslots]
+            s1 += _seq32(t)
+            s2 += _seq32(t * t)
+    return s1, s2
+
+
+HALF_MISTAKES = ('fp32_chains_h', 'truncate_half', 'no_unscale', 'mask_ge', 'drop_row')
+
+
+def bn_emulate_h(inp, spec, mistake=None, pgs=1.0):
+    """bn_emulate for the binary16 operator: sequential fp64 statistics, sequential fp32 backward sums, fp32 element arithmetic, one
+    round-to-nearest-even store of y, dx and dres.  `mistake`: one of HALF_MISTAKES."""
+    f = np.float32
+    x, dy = inp['x'], inp['dy']
+    n, c = x.shape
+    cf = spec.get('count_factor', 1)
+    keep = np.ones(n, dtype=bool)
+    if mistake == 'drop_row':
+        keep[n - 1] = False
+    gamma, beta = f64(inp['gamma']), f64(inp['beta'])
+    if mistake == 'fp32_chains_h':
+        s1, s2 = _chains32(x, c)
+    else:
+        xs = f64(x[keep])
+        s1, s2 = _seq64(xs), _seq64(xs * xs)
+    m = s1 / n
+    var = np.maximum(s2 / n - m * m, 0.0)
+    nn = n * cf
+    unb = var * nn / (nn - 1) if nn > 1 else var
+    mom = float(f(MOMENTUM))
+    got = {'running_mean': ((1 - mom) * f64(inp['rm0']) + mom * m).astype(f),
+           'running_var': ((1 - mom) * f64(inp['rv0']) + mom * unb).astype(f)}
+    inv = 1.0 / np.sqrt(var + float(f(EPS)))
+    mean32, inv32 = m.astype(f), inv.astype(f)
+    sc32, sh32 = (gamma * inv).astype(f), (beta - m * gamma * inv).astype(f)
+    got.update(mean=mean32, invstd=inv32, scale=sc32, shift=sh32)
+    v = (f64(x) * f64(sc32) + f64(sh32)).astype(f)                         # an fma: one rounding
+    if spec['res']:
+        v = v + inp['res']
+    rnd = lambda a: _round_half(a, mistake == 'truncate_half')
+    mask = None
+    if spec['relu']:
+        y = rnd(np.maximum(v, f(0)))
+        w = y if spec['res'] else v                                        # the stored output's sign / the fp32 value's
+        mask = (w >= 0) if mistake == 'mask_ge' else (w > 0)
+        if not spec['res']:
+            got['mask'] = mask
+    else:
+        y = rnd(v)
+    got['y'] = y
+    g = dy * mask.astype(f) if mask is not None else dy
+    xh = (x - mean32) * inv32
+    sg, sgx = _seq32(g[keep]), _seq32((g * xh)[keep])
+    s = f(1.0) if mistake == 'no_unscale' else f(pgs)
+    got.update(dbeta=sg * s, dgamma=sgx * s)
+    inv_n = f(1.0 / n)
+    got['dx'] = rnd((inp['gamma'] * inv32) * (g - sg * inv_n - xh * (sgx * inv_n)))
+    if spec['res']:
+        got['dres'] = rnd(g)
     return got

@@ -1,7 +1,8 @@
 """The float64 restatement of BatchNorm, segment pooling, ReLU and add (tests/_norm_rule.py) against float64 torch, its tie and
 empty-segment conventions against hand-computed cases, and its bounds against (a) an fp32 evaluation of the same formulas in an
 order unlike the kernels' -- they must not be too tight -- and (b) deliberate mistakes -- they must not be too loose -- on the very
-cases tests/test_gpu_norm.py runs.  No GPU.
+cases tests/test_gpu_norm.py runs; the same for the binary16 operator and the members of a SyncBN group (tests/test_gpu_norm_half.py),
+with the binary16 rounding conventions by hand.  No GPU.
 """
 import functools
 
@@ -266,3 +267,111 @@ def test_oracle_max_pool_follows_the_rule_on_ties():
         (o * torch.from_numpy(c['dout'])).sum().backward()
         ref = R.seg_rule(c['x'], c['ids'], c['n_seg'], 'max', c['dout'])
         assert np.array_equal(o.detach().numpy(), ref['out']) and np.array_equal(x.grad.numpy(), ref['dx']), (name, fl)
+
+
+# ------------------------------------------------------------------ binary16 BatchNorm: conventions, bounds, mistakes
+def test_half_rounding_conventions_by_hand():
+    h = lambda v: float(R.to_half(np.float32(v)))
+    # ties go to the even neighbour: the spacing is 2 in [2048, 4096)
+    assert h(2049.0) == 2048.0 and h(2051.0) == 2052.0 and h(2050.0) == 2050.0
+    # subnormals are 2^-24 apart; half of the smallest one is a tie and goes to (even) zero, anything above it rounds up
+    assert h(2.0 ** -24) == 2.0 ** -24 and h(2.0 ** -25) == 0.0 and h(1.5 * 2.0 ** -25) == 2.0 ** -24
+    assert h(3 * 2.0 ** -25) == 2.0 ** -23                                                  # 1.5 subnormal steps: tie to even (2)
+    assert h(2.0 ** -14 - 2.0 ** -25) == 2.0 ** -14                                         # the largest subnormal + half a step: tie to even
+    # the largest finite value; the rule clips before it converts
+    assert h(65504.0) == 65504.0 and h(65519.0) == 65504.0 and h(1e9) == 65504.0 and h(-1e9) == -65504.0
+    with np.errstate(over='ignore'):                                                         # IEEE: finite below 65520, infinite from there
+        assert np.float32(65519.0).astype(np.float16) == np.float16(65504.0) and np.isinf(np.float32(65520.0).astype(np.float16))
+    # the spacing table of the bound
+    assert R.half_spacing(0.0) == 2.0 ** -24 and R.half_spacing(2.0 ** -14) == 2.0 ** -24 and R.half_spacing(2.0 ** -13) == 2.0 ** -23
+    assert R.half_spacing(1.0) == 2.0 ** -10 and R.half_spacing(1.999) == 2.0 ** -10 and R.half_spacing(2048.0) == 2.0
+    assert R.half_spacing(65504.0) == 32.0 and R.half_spacing(1e6) == 32.0
+    for v in (1e-7, 3e-5, 0.3, 1000.3, 40000.0):                                            # ... is numpy's
+        assert R.half_spacing(v) == float(np.spacing(np.float16(v)))
+    # one store: 2049 known to +-0.25 may store as 2048 or 2050 -- a distance of at most 0.25 + 1 from the rule's value
+    assert float(R.half_store(2049.0, 0.25)) == 1.25
+    # truncation and the emulation's rounding
+    assert R._round_half(np.float32([2049.0, 2051.0, -2051.0]), True).tolist() == [2048.0, 2050.0, -2050.0]
+    assert R._round_half(np.float32([2049.0, 2051.0, -2051.0])).tolist() == [2048.0, 2052.0, -2052.0]
+    # the launch geometry's chain lengths
+    assert R.chain_len(5000, 96) == 25 and R.chain_len(5000, 256) == 63 and R.chain_len(2049, 512) == 114
+    assert R.chain_len(256, 1024) == 256 and R.chain_len(327680, 256) == 64 and R.chain_len(2, 4) == 1
+    assert R.is_pow2(1.0 / 1024) and R.is_pow2(1.0) and not R.is_pow2(np.float32(1.0 / 1000))
+
+
+@functools.lru_cache(maxsize=4)
+def _hinp(name):
+    return R.half_case_input(name)
+
+
+@pytest.mark.parametrize('name', list(R.HALF_CASES))
+def test_half_emulation_passes_and_few_elements_are_borderline(name):
+    spec, inp = R.HALF_CASES[name], _hinp(name)
+    n, c = inp['x'].shape
+    assert (n, c) == (spec['n'], spec['c']) and not np.any(inp['dy'] == 0)
+    assert np.abs(inp['x']).max() < R.H_MAX
+    if n >= 255:                                                                            # the columns are still what they claim
+        m, v = R.bn_stats(inp['x'])
+        for j in range(min(c, 8)):
+            k, sd = R.kind_of(j), np.sqrt(v[j])
+            if k in ('ratio30', 'ratio100', 'ratio1000'):
+                assert 0.8 * float(k[5:]) < abs(m[j]) / sd < 1.25 * float(k[5:]), (k, m[j], sd)
+            elif k == 'const':
+                assert v[j] == 0.0
+    for pgs in (1.0, 1.0 / 1024, 1.0 / 1000):
+        got = R.bn_emulate_h(inp, spec, pgs=pgs)
+        bad, share = R.bn_check_half(name, inp, spec, got, pgs=pgs, quiet=pgs != 1.0)
+        assert not bad, (name, pgs, bad)
+        assert share <= 1e-3, (name, share)
+
+
+HALF_LOOSE_ON = ('stats_h-n257-c96-res1-relu1-ldc+4', 'stats_h-n2-c4-res1-relu1', 'stats_h-n5000-c256-res1-relu1',
+                 'stats_h-n5000-c96-res0-relu1', 'sync_h-n257-c32-res0-relu1')
+
+
+@pytest.mark.parametrize('mistake', [m for m in R.HALF_MISTAKES if m != 'fp32_chains_h'])
+def test_a_deliberate_half_mistake_fails(mistake):
+    failed = []
+    for name in HALF_LOOSE_ON:
+        spec, inp = R.HALF_CASES[name], _hinp(name)
+        bad, _ = R.bn_check_half(name, inp, spec, R.bn_emulate_h(inp, spec, mistake, pgs=1.0 / 1024), pgs=1.0 / 1024, quiet=True)
+        if bad:
+            failed.append((name, [b.split(':')[0] for b in bad]))
+    print(mistake, failed)
+    assert failed, 'the bounds let the mistake %s pass on every case' % mistake
+    named = {q for _, qs in failed for q in qs}
+    want = {'truncate_half': {'y', 'dx'}, 'no_unscale': {'dbeta', 'dgamma'}, 'mask_ge': {'dres'}, 'drop_row': {'mean'}}[mistake]
+    assert want <= named, (mistake, named)
+
+
+@pytest.mark.parametrize('name', [k for k, s in R.HALF_CASES.items() if s['path'] in ('stats_h', 'sync_h') and s['n'] >= 5000
+                                  and not s.get('tiles')])
+def test_fp32_chains_of_the_half_statistics_fail_the_constants(name):
+    """bn_stats_h_kernel as it was (fp32 chains per thread in the launch geometry, fp64 from the block combine on), SIMULATED in
+    numpy: invstd or scale must miss its bound on every such case with n >= 5000 -- on the |mean| >= 30 sigma columns."""
+    spec, inp = R.HALF_CASES[name], _hinp(name)
+    got = R.bn_emulate_h(inp, spec, 'fp32_chains_h')
+    fwd = R.bn_forward(inp['x'], inp['gamma'], inp['beta'], None, False, (inp['rm0'], inp['rv0']), count_factor=spec.get('count_factor', 1))
+    cb = R.const_bounds(inp['x'], inp['gamma'], fwd, count_factor=spec.get('count_factor', 1))
+    kinds = np.array([R.kind_of(j) for j in range(spec['c'])])
+    over = {}
+    for q in ('invstd', 'scale'):
+        r = np.abs(got[q].astype(np.float64) - fwd[q]) / cb[q]
+        over[q] = float(r.max())
+        for k in ('ratio30', 'ratio100', 'ratio1000', 'ratio0.5'):
+            print(name, q, k, 'error / bound: max %.3g' % r[kinds == k].max())
+        assert r[(kinds == 'ratio0') | (kinds == 'ratio0.5')].max() <= 1.0
+    assert over['invstd'] > 1.0 or over['scale'] > 1.0, over
+    bad, _ = R.bn_check_half(name, inp, spec, got, quiet=True)
+    assert any(b.startswith(('invstd', 'scale')) for b in bad), bad
+
+
+@pytest.mark.parametrize('name', list(R.GROUP_CASES))
+def test_group_members_are_the_syncbn_rule(name):
+    n, cs = R.GROUP_CASES[name]
+    for j, inp in enumerate(R.group_case_inputs(name)):
+        assert inp['x'].shape == (n, cs[j])
+        bad, _ = R.bn_check('%s[%d]' % (name, j), inp, R.GROUP_SPEC, R.bn_emulate(inp, R.GROUP_SPEC), quiet=True)
+        assert not bad, (name, j, bad)
+        bad, _ = R.bn_check('%s[%d]' % (name, j), inp, R.GROUP_SPEC, R.bn_emulate(inp, R.GROUP_SPEC, 'no_bessel'), quiet=True)
+        assert bad and all(b.startswith('running_var') for b in bad), (name, j, bad)        # 2n rows in the unbiased factor
