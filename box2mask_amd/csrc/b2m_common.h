@@ -45,6 +45,9 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // rulebooks with at least this many tiles carry XCD work boundaries and a dispatch order (b2m_rulebook_balance), and the
 // convolutions use them
 #define B2M_BALANCE_MIN_TILES 64
+// longest XCD run b2m_rulebook_balance allows, in tiles: 1.25 x an eighth, rounded up.  The balance kernel cuts the runs by
+// it and the convolutions size their launch grids by it (no host read of the boundaries).
+#define B2M_XCD_CAP(ntiles) (((ntiles) * 5 + 31) / 32)
 
 __device__ __forceinline__ uint64_t b2m_pack(int b, int x, int y, int z) {
     return ((uint64_t)(uint32_t)b << 48) | ((uint64_t)(uint32_t)x << 32) | ((uint64_t)(uint32_t)y << 16) |

@@ -210,7 +210,6 @@ __device__ __forceinline__ int64_t wg_index(int64_t nwg, int64_t chunk) {
 // Work-balanced form: XCD x owns the tiles [start[x], start[x+1]) that b2m_rulebook_balance chose (equal WORK, not
 // equal tile counts), `per_tile` workgroups each; hardware workgroup 8*j + x is the j-th of XCD x.  The grid covers the
 // longest run the balance kernel allows (B2M_XCD_CAP tiles); workgroups past the end of their XCD's run leave.
-#define B2M_XCD_CAP(ntiles) (((ntiles) * 5 + 31) / 32)
 __device__ __forceinline__ int64_t wg_index_balanced(const int32_t* __restrict__ start, int64_t per_tile) {
     const int x = blockIdx.x & 7;
     const int64_t j = blockIdx.x >> 3;
@@ -722,11 +721,10 @@ __global__ __launch_bounds__(256, 4) void conv_stem_kernel(ConvArgs a) {
 #include "conv_fwd_flow.h"
 #include "conv_1x1.h"
 
-static int env_flag(const char* name, int dflt);
 static inline int conv_kc(int cin) { return cin >= 16 ? 16 : 8; }
 // strip width in 16-column tiles: 48-column strips for the 96-channel spatial layers (A fragments reused 3x:
 // +7 % in the A/B of tools/bench_conv.py), else 32 (1x1 layers measured faster with 32)
-static inline int conv_tw(int cout, int K) { return (cout % 48 == 0 && K > 1 && env_flag("B2M_CONV_TW3", 1)) ? 3 : 2; }
+static inline int conv_tw(int cout, int K) { return (cout % 48 == 0 && K > 1 && b2m_env_int("B2M_CONV_TW3", 1)) ? 3 : 2; }
 
 extern "C" int64_t b2m_weight_pack_size(int32_t K, int32_t cin, int32_t cout) {
     const int KC = conv_kc(cin);
@@ -914,6 +912,44 @@ extern "C" int b2m_weight_pack_run(const void* plan_dev, int32_t n, int64_t tota
     return B2M_OK;
 }
 
+// ---- launch planning shared by the convolution entries (host side)
+// "32-bit addressable": a tensor of `rows` rows of `ld` elements of `esz` bytes whose row numbers fit a 24-bit multiply and whose byte
+// offsets fit 32 bits -- rows < 2^24, pitch < 2^22 elements, tensor < 4 GiB (ConvArgs::fast32, WgradArgs::fast32)
+static inline bool addr32(int64_t rows, int64_t ld, int esz) {
+    return rows < (1 << 24) && ld < (1 << 22) && rows * ld * esz < (1ll << 32);
+}
+// both sources of a forward convolution (a missing second source comes with pitch 0)
+static inline bool addr32(int64_t rows, int64_t ld1, int64_t ld2, int esz) { return addr32(rows, ld1, esz) && addr32(rows, ld2, esz); }
+// The ConvArgs fields every forward entry fills alike: sources, weights, rulebook, output rows and tiles, output, and the strips of a
+// launch with 16 * TW columns each.  Everything else is zero (no statistics, no epilogue, plain XCD order) until the entry sets it.
+static inline ConvArgs conv_args(const float* x1, int64_t ldx1, int c1, const float* x2, int64_t ldx2, int c2, const float* wp, int K,
+                                 const int32_t* rb_in, const uint8_t* rb_out, const int32_t* rb_cnt, int64_t n_out, float* y, int64_t ldy,
+                                 int cout, int TW) {
+    ConvArgs a{};
+    a.x1 = x1; a.ldx1 = ldx1; a.c1 = c1; a.x2 = x2; a.ldx2 = ldx2; a.c2 = c2;
+    a.wp = wp; a.K = K;
+    a.rb_in = rb_in; a.rb_out = rb_out; a.rb_cnt = rb_cnt;
+    a.n_out = n_out; a.ntiles = cdiv64(n_out, B2M_TILE);
+    a.y = y; a.ldy = ldy; a.cout = cout;
+    a.nstrips = (cout + 16 * TW - 1) / (16 * TW);
+    return a;
+}
+// XCD order of a forward launch of a.nwg workgroups, each holding `wpb` of a tile's `items_per_tile` (strip, slice) items: sets
+// a.xcd_per -- contiguous eighths, xcd_order() -- and returns the grid.  `balanced`: the entry's own condition for the work-balanced
+// form (wg_index_balanced), which then also needs a rulebook with XCD boundaries (B2M_BALANCE_MIN_TILES); it sets a.xcd_start,
+// a.tile_order and a.wg_per_tile, and the grid covers the longest run the balance kernel allows.
+static inline unsigned conv_xcd_plan(ConvArgs& a, int64_t items_per_tile, int wpb, bool balanced) {
+    const int64_t xcd_tiles = b2m_env_int("B2M_XCD", 1) ? (1 << 30) : 0;        // (finer chunks measured equal or slower: one run per XCD)
+    const XcdOrder o = xcd_order(a.nwg, xcd_tiles * items_per_tile / wpb);
+    a.xcd_per = o.chunk;
+    // XCD runs of equal work (the tail of rb_cnt, b2m_rulebook_balance) instead of equal tile counts
+    if (!(balanced && a.ntiles >= B2M_BALANCE_MIN_TILES && xcd_tiles > 0 && b2m_env_int("B2M_XCD_BALANCE", 1))) return o.grid;
+    a.xcd_start = a.rb_cnt + (int64_t)a.K * a.ntiles;
+    a.tile_order = b2m_env_int("B2M_XCD_ORDER", 1) ? a.xcd_start + 16 + a.ntiles : nullptr;
+    a.wg_per_tile = items_per_tile / wpb;
+    return (unsigned)(8 * B2M_XCD_CAP(a.ntiles) * a.wg_per_tile);
+}
+
 struct ConvEpilogue { const float* scale; const float* shift; const float* res; int64_t ld_res; int relu; };
 static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float* x2, int64_t ldx2, int32_t c2,
                          int64_t n_in, const float* wp, int32_t K, const float* bias, const int32_t* rb_in,
@@ -941,17 +977,9 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
     // fast path: every chunk is complete and every gathered segment is aligned; otherwise per-element loads
     const bool fast = c1 % KC == 0 && c2 % KC == 0 && ldx1 % KS == 0 && (c2 == 0 || ldx2 % KS == 0) &&
                       ((uintptr_t)x1 % (4 * KS)) == 0 && ((uintptr_t)x2 % (4 * KS)) == 0;
-    ConvArgs a{};
-    a.x1 = x1; a.ldx1 = ldx1; a.c1 = c1; a.x2 = x2; a.ldx2 = ldx2; a.c2 = c2;
-    a.wp = wp; a.K = K; a.bias = bias;
-    a.rb_in = rb_in; a.rb_out = rb_out; a.rb_cnt = rb_cnt;
-    a.n_out = n_out; a.ntiles = cdiv64(n_out, B2M_TILE);
-    a.y = y; a.ldy = ldy; a.cout = cout; a.accumulate = accumulate;
-    a.stats = nullptr; a.chain = 0;
-    a.ep_scale = a.ep_shift = a.ep_res = nullptr; a.ld_res = 0; a.ep_relu = 0;
-    a.xcd_start = nullptr; a.wg_per_tile = 0; a.tile_order = nullptr;
     const int TW = conv_tw(cout, K);
-    a.nstrips = (cout + 16 * TW - 1) / (16 * TW);
+    ConvArgs a = conv_args(x1, ldx1, c1, x2, ldx2, c2, wp, K, rb_in, rb_out, rb_cnt, n_out, y, ldy, cout, TW);
+    a.bias = bias; a.accumulate = accumulate;
     a.vec_store = (ldy % 4 == 0 && ((uintptr_t)y % 16) == 0) ? 1 : 0;
     // the inference epilogue needs whole 16-byte column groups everywhere it touches
     const bool ep_ok = ep && ep->scale && ep->shift && a.vec_store && cout % 4 == 0 && !accumulate && !bias &&
@@ -972,7 +1000,7 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
     // (round 5: layers with one or two 16-channel chunks -- the 32-channel blocks of level 1, 4.5 k items at the benchmark's
     // size -- have so little work per (offset, slice) that the split costs more than the second round of waves: 52 -> 56
     // TFLOP/s un-split; they split only below 4096 items)
-    const int64_t target = env_flag("B2M_DETERMINISTIC", 0) ? 0 : env_flag("B2M_CONV_TARGET", cin <= 32 ? 4096 : 6144);
+    const int64_t target = b2m_env_int("B2M_DETERMINISTIC", 0) ? 0 : b2m_env_int("B2M_CONV_TARGET", cin <= 32 ? 4096 : 6144);
     if (items0 < target && K > 1) {
         nslice = (int)cdiv64(target, items0);
         if (nslice > 16) nslice = 16;
@@ -984,7 +1012,7 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
             // At most 4 slices (one workgroup per item: plain stores, no zero-fill, no atomics, and the epilogue can
             // take the BatchNorm column sums) unless the map is tiny: measured equal or faster than 8..16 slices from
             // 8 tiles up (the atomic combine and the memset eat what the extra waves gain), slower below.
-            const int cap = env_flag("B2M_CONV_MAXSLICE", a.ntiles >= 8 ? 4 : 16);
+            const int cap = b2m_env_int("B2M_CONV_MAXSLICE", a.ntiles >= 8 ? 4 : 16);
             if (nslice > cap) nslice = cap;
         }
     }
@@ -992,27 +1020,24 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
     // chunk steps gets short; the slices still combine in LDS / with atomics
     int ncs = 1;
     const int nchunk_h = (cin + KC - 1) / KC;
-    while (nslice > 1 && ncs < 4 && items0 * nslice * ncs < env_flag("B2M_CONV_CHUNK_ITEMS", 2048) && nchunk_h / (ncs * 2) >= 2 &&
-           env_flag("B2M_CONV_CHUNKSPLIT", 1)) ncs *= 2;
+    while (nslice > 1 && ncs < 4 && items0 * nslice * ncs < b2m_env_int("B2M_CONV_CHUNK_ITEMS", 2048) && nchunk_h / (ncs * 2) >= 2 &&
+           b2m_env_int("B2M_CONV_CHUNKSPLIT", 1)) ncs *= 2;
     nslice *= ncs;
     // (round 6) medium maps that run un-split -- a few rounds of long-lived waves, tools/residency.py: 14-18 % of such a launch is
     // its drain -- as TWO slices per item (workgroups of two waves that combine in LDS): half the wave lifetime, half the drain.
     // B2M_CONV_SPLIT2 = largest item count that takes this form (0: off)
     // -- only where the hand-issued flow kernel runs (the one kernel with a two-wave instantiation)
-    const bool fast32_ok = n_in < (1 << 24) && ldx1 < (1 << 22) && ldx2 < (1 << 22) && n_in * ldx1 * 4 < (1ll << 32) &&
-                           n_in * ldx2 * 4 < (1ll << 32) && env_flag("B2M_CONV_FAST32", 1);
+    a.fast32 = (addr32(n_in, ldx1, ldx2, 4) && b2m_env_int("B2M_CONV_FAST32", 1)) ? 1 : 0;
     bool split2 = false;
-    if (nslice == 1 && K >= 8 && rb_in != nullptr && fast && KC == 16 && fast32_ok && (cin / 16) % 2 == 0 && cin >= 32 &&
-        env_flag("B2M_CONV_PIPE", 2) && env_flag("B2M_CONV_HANDLOADS", 1) && !env_flag("B2M_PIPE_DBG", 0) &&
-        !env_flag("B2M_DETERMINISTIC", 0) && items0 >= target && items0 < env_flag("B2M_CONV_SPLIT2", 0)) {
+    if (nslice == 1 && K >= 8 && rb_in != nullptr && fast && KC == 16 && a.fast32 && (cin / 16) % 2 == 0 && cin >= 32 &&
+        b2m_env_int("B2M_CONV_PIPE", 2) && b2m_env_int("B2M_CONV_HANDLOADS", 1) && !b2m_env_int("B2M_PIPE_DBG", 0) &&
+        !b2m_env_int("B2M_DETERMINISTIC", 0) && items0 >= target && items0 < b2m_env_int("B2M_CONV_SPLIT2", 0)) {
         nslice = 2;
         split2 = true;
     }
     a.ncs = ncs;
     a.nslice = nslice;
-    a.wg_combine = ((nslice > 1 && nslice % 4 == 0 && env_flag("B2M_CONV_WGCOMBINE", 1)) || split2) ? 1 : 0;
-    a.fast32 = (n_in < (1 << 24) && ldx1 < (1 << 22) && ldx2 < (1 << 22) && n_in * ldx1 * 4 < (1ll << 32) &&
-                n_in * ldx2 * 4 < (1ll << 32) && env_flag("B2M_CONV_FAST32", 1)) ? 1 : 0;
+    a.wg_combine = ((nslice > 1 && nslice % 4 == 0 && b2m_env_int("B2M_CONV_WGCOMBINE", 1)) || split2) ? 1 : 0;
     static const float* zeros_addr = nullptr;
     if (!zeros_addr) B2M_HIP(hipGetSymbolAddress((void**)&zeros_addr, HIP_SYMBOL(g_zeros)));
     a.zeros = zeros_addr;
@@ -1020,14 +1045,12 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
         B2M_HIP(hipMemset2DAsync(y, (size_t)ldy * sizeof(float), 0, (size_t)cout * sizeof(float), (size_t)n_out, st));
     const int64_t items = items0 * nslice;
     a.nwg = cdiv64(items, 4);
-    // XCD-aware order: contiguous eighths; a workgroup holds 4 (tile, strip, slice) items
-    const int64_t xcd_tiles = env_flag("B2M_XCD", 1) ? (1 << 30) : 0;        // (finer chunks measured equal or slower: one run per XCD)
-    const XcdOrder xo = xcd_order(a.nwg, xcd_tiles * a.nstrips * nslice / 4);
-    a.xcd_per = xo.chunk;
-    const unsigned grid = xo.grid;
+    // XCD-aware order: contiguous eighths; a workgroup holds 4 (tile, strip, slice) items (the generic, stem and 1x1 kernels; the
+    // flow kernel plans its own below)
+    const unsigned grid = conv_xcd_plan(a, (int64_t)a.nstrips * nslice, 4, false);
     const bool ident = rb_in == nullptr;
     // 1x1 layers with whole 16-channel chunks: the streaming-GEMM kernel (conv_1x1.h), accumulators in registers
-    if (ident && fast && KC == 16 && a.fast32 && n_in >= n_out && env_flag("B2M_CONV_1X1", 1)) {
+    if (ident && fast && KC == 16 && a.fast32 && n_in >= n_out && b2m_env_int("B2M_CONV_1X1", 1)) {
         int spw = a.nstrips % 3 == 0 ? 3 : a.nstrips % 2 == 0 ? 2 : 1;
         if (a.ntiles * (a.nstrips / spw) < 2048) spw = 1;       // few rows (the heads on segments): one wave per strip
         const int64_t g1 = a.ntiles * (a.nstrips / spw);
@@ -1045,13 +1068,13 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
     {
         const int nc = cin / 16;
         // (round 5: the three-steps-in-flight form of the fp32 kernel -- B2M_CONV_PIPE=3, measured +-0.3 % in rounds 2 and 4 -- is gone)
-        const int depth = env_flag("B2M_CONV_PIPE", 2) ? 2 : 0;
-        const bool split_ok = nslice == 1 || (a.wg_combine && env_flag("B2M_CONV_FLOW_SPLIT", 1));
+        const int depth = b2m_env_int("B2M_CONV_PIPE", 2) ? 2 : 0;
+        const bool split_ok = nslice == 1 || (a.wg_combine && b2m_env_int("B2M_CONV_FLOW_SPLIT", 1));
         if (depth >= 2 && !ident && fast && KC == 16 && split_ok && a.fast32 && nc % ncs == 0 && (nc / ncs) % depth == 0 &&
             nc / ncs >= depth) {
             const int wpb = nslice == 1 ? 1 : split2 ? 2 : 4;
             B2M_CHECK_ARG(items0 < (1ll << 31), "too many (tile, strip) items");      // (32-bit index arithmetic in the kernel)
-            a.chain = (wpb == 1 && env_flag("B2M_CONV_CHAIN", 1)) ? 1 : 0;
+            a.chain = (wpb == 1 && b2m_env_int("B2M_CONV_CHAIN", 1)) ? 1 : 0;
             // the workgroup that writes a (tile, strip) sees its final values: un-split maps, or exactly 4 slices
             // combined in LDS and stored plainly
             if (tile_stats && (nslice == 1 || ((nslice == 4 || split2) && !accumulate))) {
@@ -1061,55 +1084,48 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
             // (the workgroup that writes a (tile, strip) holds its final values: un-split, or exactly 4 slices combined in LDS)
             if (ep_ok && (nslice == 1 || nslice == 4 || split2)) use_epilogue();
             a.nwg = cdiv64(items, wpb);
-            XcdOrder fo = xcd_order(a.nwg, xcd_tiles * a.nstrips * nslice / wpb);
-            a.xcd_per = fo.chunk;
-            // XCD runs of equal work (the tail of rb_cnt, b2m_rulebook_balance) instead of equal tile counts
-            if (a.ntiles >= B2M_BALANCE_MIN_TILES && xcd_tiles > 0 && (a.nstrips * nslice) % wpb == 0 && env_flag("B2M_XCD_BALANCE", 1)) {
-                a.xcd_start = rb_cnt + (int64_t)K * a.ntiles;
-                a.tile_order = env_flag("B2M_XCD_ORDER", 1) ? a.xcd_start + 16 + a.ntiles : nullptr;
-                a.wg_per_tile = a.nstrips * nslice / wpb;
-                fo.grid = (unsigned)(8 * B2M_XCD_CAP(a.ntiles) * a.wg_per_tile);
-            }
-            const int dbg = env_flag("B2M_PIPE_DBG", 0);      // diagnostic builds, wrong results: tools/pipe_breakdown.py
-            const int hl = env_flag("B2M_CONV_HANDLOADS", 1);     // hand-issued operand loads, absent row groups masked (conv_fwd_flow.h)
+            // (balanced runs: whole workgroups per tile)
+            const unsigned fgrid = conv_xcd_plan(a, (int64_t)a.nstrips * nslice, wpb, (a.nstrips * nslice) % wpb == 0);
+            const int dbg = b2m_env_int("B2M_PIPE_DBG", 0);      // diagnostic builds, wrong results: tools/pipe_breakdown.py
+            const int hl = b2m_env_int("B2M_CONV_HANDLOADS", 1);     // hand-issued operand loads, absent row groups masked (conv_fwd_flow.h)
             if (hl && depth == 2 && dbg == 32 && wpb == 1 && TW == 3) {       // diagnostic: the walk twice per wave
-                conv_fwd_flow_kernel<2, 3, 32, 1, 1><<<fo.grid, 64, 0, st>>>(a);
+                conv_fwd_flow_kernel<2, 3, 32, 1, 1><<<fgrid, 64, 0, st>>>(a);
                 B2M_LAUNCH_CHECK();
                 return B2M_OK;
             }
             if (hl && depth == 2 && dbg == 8 && wpb == 1 && TW == 3) {        // diagnostic: every load, flush and list step, no MFMA
-                conv_fwd_flow_kernel<2, 3, 8, 1, 1><<<fo.grid, 64, 0, st>>>(a);    // (hand-issued loads cannot be optimised away)
+                conv_fwd_flow_kernel<2, 3, 8, 1, 1><<<fgrid, 64, 0, st>>>(a);    // (hand-issued loads cannot be optimised away)
                 B2M_LAUNCH_CHECK();
                 return B2M_OK;
             }
             if (hl && depth == 2 && !dbg) {
                 if (wpb == 2) {
-                    if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 2, 1><<<fo.grid, 128, 0, st>>>(a);
-                    else conv_fwd_flow_kernel<2, 2, 0, 2, 1><<<fo.grid, 128, 0, st>>>(a);
+                    if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 2, 1><<<fgrid, 128, 0, st>>>(a);
+                    else conv_fwd_flow_kernel<2, 2, 0, 2, 1><<<fgrid, 128, 0, st>>>(a);
                 } else if (wpb == 4) {
-                    if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 4, 1><<<fo.grid, 256, 0, st>>>(a);
-                    else conv_fwd_flow_kernel<2, 2, 0, 4, 1><<<fo.grid, 256, 0, st>>>(a);
+                    if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 4, 1><<<fgrid, 256, 0, st>>>(a);
+                    else conv_fwd_flow_kernel<2, 2, 0, 4, 1><<<fgrid, 256, 0, st>>>(a);
                 } else {
-                    if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 1, 1><<<fo.grid, 64, 0, st>>>(a);
-                    else conv_fwd_flow_kernel<2, 2, 0, 1, 1><<<fo.grid, 64, 0, st>>>(a);
+                    if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 1, 1><<<fgrid, 64, 0, st>>>(a);
+                    else conv_fwd_flow_kernel<2, 2, 0, 1, 1><<<fgrid, 64, 0, st>>>(a);
                 }
                 B2M_LAUNCH_CHECK();
                 return B2M_OK;
             }
             if (wpb == 4) {
-                if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 4><<<fo.grid, 256, 0, st>>>(a);
-                else conv_fwd_flow_kernel<2, 2, 0, 4><<<fo.grid, 256, 0, st>>>(a);
+                if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 4><<<fgrid, 256, 0, st>>>(a);
+                else conv_fwd_flow_kernel<2, 2, 0, 4><<<fgrid, 256, 0, st>>>(a);
             } else if (dbg && TW == 3) {          // diagnostic builds of tools/pipe_breakdown.py (wrong results)
                 switch (dbg) {
-                    case 1: conv_fwd_flow_kernel<2, 3, 1><<<fo.grid, 64, 0, st>>>(a); break;
-                    case 2: conv_fwd_flow_kernel<2, 3, 2><<<fo.grid, 64, 0, st>>>(a); break;
-                    case 4: conv_fwd_flow_kernel<2, 3, 4><<<fo.grid, 64, 0, st>>>(a); break;
-                    case 8: conv_fwd_flow_kernel<2, 3, 8><<<fo.grid, 64, 0, st>>>(a); break;
-                    default: conv_fwd_flow_kernel<2, 3, 6><<<fo.grid, 64, 0, st>>>(a); break;
+                    case 1: conv_fwd_flow_kernel<2, 3, 1><<<fgrid, 64, 0, st>>>(a); break;
+                    case 2: conv_fwd_flow_kernel<2, 3, 2><<<fgrid, 64, 0, st>>>(a); break;
+                    case 4: conv_fwd_flow_kernel<2, 3, 4><<<fgrid, 64, 0, st>>>(a); break;
+                    case 8: conv_fwd_flow_kernel<2, 3, 8><<<fgrid, 64, 0, st>>>(a); break;
+                    default: conv_fwd_flow_kernel<2, 3, 6><<<fgrid, 64, 0, st>>>(a); break;
                 }
             } else {
-                if (TW == 3) conv_fwd_flow_kernel<2, 3><<<fo.grid, 64, 0, st>>>(a);
-                else conv_fwd_flow_kernel<2, 2><<<fo.grid, 64, 0, st>>>(a);
+                if (TW == 3) conv_fwd_flow_kernel<2, 3><<<fgrid, 64, 0, st>>>(a);
+                else conv_fwd_flow_kernel<2, 2><<<fgrid, 64, 0, st>>>(a);
             }
             B2M_LAUNCH_CHECK();
             return B2M_OK;
@@ -1117,7 +1133,7 @@ static int conv_fwd_impl(const float* x1, int64_t ldx1, int32_t c1, const float*
     }
     // the first layer's shape (one 8-channel chunk, one 32-column strip, un-split): the hand-pipelined walk over the offsets
     if (KC == 8 && !ident && fast && cin == 8 && c2 == 0 && nslice == 1 && a.nstrips == 1 && TW == 2 && a.fast32 &&
-        env_flag("B2M_CONV_STEM", 1)) {
+        b2m_env_int("B2M_CONV_STEM", 1)) {
         if (tile_stats) {                      // the workgroup that writes a tile sees its final values (un-split)
             a.stats = tile_stats;
             if (wrote_stats) *wrote_stats = 1;
@@ -1192,17 +1208,11 @@ extern "C" int b2m_conv_up(const float* x1, int64_t ldx1, int32_t c1, const floa
     B2M_CHECK_ARG(c2 == 0 || x2 != nullptr, "x2 is NULL");
     const int cin = c1 + c2;
     const int TW = conv_tw(cout, K);
-    ConvArgs a{};
-    a.x1 = x1; a.ldx1 = ldx1; a.c1 = c1; a.x2 = x2; a.ldx2 = ldx2; a.c2 = c2;
-    a.wp = wp; a.K = K; a.bias = bias;
-    a.rb_in = rb_in; a.rb_out = rb_out; a.rb_cnt = rb_cnt;
-    a.n_out = n_coarse; a.ntiles = cdiv64(n_coarse, B2M_TILE);
-    a.y = y; a.ldy = ldy; a.cout = cout; a.accumulate = accumulate;
-    a.stats = nullptr; a.chain = 0;
+    // (n_out = n_coarse: the scatter form is tiled over the rows it READS; y has n_fine rows)
+    ConvArgs a = conv_args(x1, ldx1, c1, x2, ldx2, c2, wp, K, rb_in, rb_out, rb_cnt, n_coarse, y, ldy, cout, TW);
+    a.bias = bias; a.accumulate = accumulate;
     a.ep_scale = scale; a.ep_shift = shift; a.ep_res = res; a.ld_res = ld_res; a.ep_relu = relu;
-    a.xcd_start = nullptr; a.wg_per_tile = 0; a.tile_order = nullptr;
-    a.nstrips = (cout + 16 * TW - 1) / (16 * TW);
-    a.vec_store = 1; a.nslice = 1; a.ncs = 1; a.wg_combine = 0; a.zeros = nullptr;
+    a.vec_store = 1; a.nslice = 1; a.ncs = 1;
     const int nc = cin / 16;
     const int64_t n_max = n_coarse > n_fine ? n_coarse : n_fine;
     const bool ok = c1 % 16 == 0 && c2 % 16 == 0 && nc >= 2 && nc % 2 == 0 && cout % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)y % 16) == 0 &&
@@ -1210,25 +1220,16 @@ extern "C" int b2m_conv_up(const float* x1, int64_t ldx1, int32_t c1, const floa
                     ((uintptr_t)wp % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0) &&
                     (!scale || (!accumulate && !bias && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)shift % 16) == 0 &&
                                 (!res || (ld_res % 4 == 0 && ld_res >= cout && ((uintptr_t)res % 16) == 0)))) &&
-                    n_max < (1 << 24) && ldx1 < (1 << 22) && ldx2 < (1 << 22) && n_coarse * ldx1 * 4 < (1ll << 32) &&
-                    n_coarse * ldx2 * 4 < (1ll << 32) &&
-                    a.ntiles * a.nstrips >= env_flag("B2M_CONV_UP_MIN_ITEMS", 450) && !env_flag("B2M_PIPE_DBG", 0) &&
-                    env_flag("B2M_CONV_UP", 1);
+                    n_max < (1 << 24) && addr32(n_coarse, ldx1, ldx2, 4) &&      // (row numbers of both maps, bytes of the sources)
+                    a.ntiles * a.nstrips >= b2m_env_int("B2M_CONV_UP_MIN_ITEMS", 450) && !b2m_env_int("B2M_PIPE_DBG", 0) &&
+                    b2m_env_int("B2M_CONV_UP", 1);
     if (!ok) return B2M_OK;
     a.fast32 = 1;
     a.nwg = a.ntiles * a.nstrips;
     B2M_CHECK_ARG(a.nwg < (1ll << 31), "too many (tile, strip) items");
-    const int64_t xcd_tiles = env_flag("B2M_XCD", 1) ? (1 << 30) : 0;
-    XcdOrder fo = xcd_order(a.nwg, xcd_tiles * a.nstrips);
-    a.xcd_per = fo.chunk;
-    if (a.ntiles >= B2M_BALANCE_MIN_TILES && xcd_tiles > 0 && env_flag("B2M_XCD_BALANCE", 1)) {
-        a.xcd_start = rb_cnt + (int64_t)K * a.ntiles;
-        a.tile_order = env_flag("B2M_XCD_ORDER", 1) ? a.xcd_start + 16 + a.ntiles : nullptr;
-        a.wg_per_tile = a.nstrips;
-        fo.grid = (unsigned)(8 * B2M_XCD_CAP(a.ntiles) * a.wg_per_tile);
-    }
-    if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 1, 1, 0, 1><<<fo.grid, 64, 0, st>>>(a);
-    else conv_fwd_flow_kernel<2, 2, 0, 1, 1, 0, 1><<<fo.grid, 64, 0, st>>>(a);
+    const unsigned fgrid = conv_xcd_plan(a, a.nstrips, 1, true);      // (one workgroup per item: balanced wherever the rulebook allows)
+    if (TW == 3) conv_fwd_flow_kernel<2, 3, 0, 1, 1, 0, 1><<<fgrid, 64, 0, st>>>(a);
+    else conv_fwd_flow_kernel<2, 2, 0, 1, 1, 0, 1><<<fgrid, 64, 0, st>>>(a);
     B2M_LAUNCH_CHECK();
     *ran = 1;
     return B2M_OK;
@@ -1249,7 +1250,7 @@ static inline int conv_h_ck(int c1, int c2) {
 // SIMD, not three or four, and halves the number of work items: on maps of a few dozen tiles it loses (level 4 256->256 111 -> 93),
 // so b2m_conv_fwd_h launches the 32-column kernel there -- on the same image (ConvArgs::img_wide).  B2M_CONV_TW4_H=0: as fp32.
 static inline int conv_tw_h(int cout, int K) {
-    if (K > 1 && cout % 64 == 0 && env_flag("B2M_CONV_TW4_H", 1)) return 4;
+    if (K > 1 && cout % 64 == 0 && b2m_env_int("B2M_CONV_TW4_H", 1)) return 4;
     return conv_tw(cout, K);
 }
 extern "C" int64_t b2m_weight_pack_h_size(int32_t K, int32_t c1, int32_t c2, int32_t cout) {      // in halfs
@@ -1407,42 +1408,30 @@ static int conv_fwd_h_impl(const void* x1, int64_t ldx1, int32_t c1, const void*
                   (!res || (ld_res % 4 == 0 && ld_res >= cout)), "row pitches: 16-byte multiples for the inputs, 8 for output / residual");
     B2M_CHECK_ARG(((uintptr_t)x1 % 16) == 0 && ((uintptr_t)x2 % 16) == 0 && ((uintptr_t)wp % 16) == 0 && ((uintptr_t)y % 8) == 0 &&
                   ((uintptr_t)res % 8) == 0 && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)shift % 16) == 0, "alignment");
-    B2M_CHECK_ARG(n_in >= 1 && n_in < (1 << 24) && ldx1 < (1 << 22) && ldx2 < (1 << 22) && n_in * ldx1 * 2 < (1ll << 32) &&
-                  n_in * ldx2 * 2 < (1ll << 32), "inputs must be 32-bit addressable (1 <= rows < 2^24, tensors < 4 GiB)");
-    ConvArgs a{};
-    a.x1 = (const float*)x1; a.ldx1 = ldx1; a.c1 = c1; a.x2 = (const float*)x2; a.ldx2 = ldx2; a.c2 = c2;
-    a.wp = (const float*)wp; a.K = K; a.bias = nullptr;
-    a.rb_in = rb_in; a.rb_out = rb_out; a.rb_cnt = rb_cnt;
-    a.n_out = n_out; a.ntiles = cdiv64(n_out, B2M_TILE);
-    a.y = (float*)y; a.ldy = ldy; a.cout = cout; a.accumulate = 0; a.stats = tile_stats; a.vec_store = 1; a.fast32 = 1;
-    a.ep_scale = scale; a.ep_shift = shift; a.ep_res = (const float*)res; a.ld_res = ld_res; a.ep_relu = relu;
-    a.xcd_start = nullptr; a.wg_per_tile = 0; a.tile_order = nullptr; a.zeros = nullptr;
+    B2M_CHECK_ARG(n_in >= 1 && addr32(n_in, ldx1, ldx2, 2), "inputs must be 32-bit addressable (1 <= rows < 2^24, tensors < 4 GiB)");
     // the image is packed for 64-column strips wherever the output channels come in 64s; a map of fewer than 256 tiles runs its
     // 32-column kernel on that image (two waves per SIMD and half the work items cost more there than the second gather)
     const int TW_img = conv_tw_h(cout, K);
-    const int TW = (TW_img == 4 && a.ntiles < env_flag("B2M_CONV_TW4_H_MIN_TILES", 256)) ? 2 : TW_img;
+    const int TW = (TW_img == 4 && cdiv64(n_out, B2M_TILE) < b2m_env_int("B2M_CONV_TW4_H_MIN_TILES", 256)) ? 2 : TW_img;
+    // (half tensors behind the struct's float pointers: the F16 kernels cast them back)
+    ConvArgs a = conv_args((const float*)x1, ldx1, c1, (const float*)x2, ldx2, c2, (const float*)wp, K, rb_in, rb_out, rb_cnt, n_out,
+                           (float*)y, ldy, cout, TW);
+    a.stats = tile_stats; a.vec_store = 1; a.fast32 = 1;
+    a.ep_scale = scale; a.ep_shift = shift; a.ep_res = (const float*)res; a.ld_res = ld_res; a.ep_relu = relu;
     a.img_wide = (TW_img == 4 && TW == 2) ? 1 : 0;
-    a.nstrips = (cout + 16 * TW - 1) / (16 * TW);
     const int CK = conv_h_ck(c1, c2), nc = (c1 + c2) / CK;
     int depth = nc % 2 == 0 ? 2 : 3;
     B2M_CHECK_ARG(CK == 32 || nc % 2 == 0, "input channels: multiples of 32 (or an even number of 16-channel chunks)");
     // small maps: the active offsets of an item dealt to the 4 waves of a workgroup (combined in LDS, plain stores); never more
     const int64_t items0 = a.ntiles * a.nstrips;
-    const int nslice = (items0 < env_flag("B2M_CONV_TARGET", 6144) && K >= 4) ? 4 : 1;
+    const int nslice = (items0 < b2m_env_int("B2M_CONV_TARGET", 6144) && K >= 4) ? 4 : 1;
     a.nslice = nslice; a.ncs = 1; a.wg_combine = nslice == 4;
     const int wpb = nslice == 1 ? 1 : 4;
     const int64_t items = items0 * nslice;
     a.nwg = cdiv64(items, wpb);
-    const int64_t xcd_tiles = env_flag("B2M_XCD", 1) ? (1 << 30) : 0;
-    XcdOrder fo = xcd_order(a.nwg, xcd_tiles * a.nstrips * nslice / wpb);
-    a.xcd_per = fo.chunk;
-    if (a.ntiles >= B2M_BALANCE_MIN_TILES && xcd_tiles > 0 && (a.nstrips * nslice) % wpb == 0 && K > 1 && env_flag("B2M_XCD_BALANCE", 1)) {
-        a.xcd_start = rb_cnt + (int64_t)K * a.ntiles;
-        a.tile_order = env_flag("B2M_XCD_ORDER", 1) ? a.xcd_start + 16 + a.ntiles : nullptr;
-        a.wg_per_tile = a.nstrips * nslice / wpb;
-        fo.grid = (unsigned)(8 * B2M_XCD_CAP(a.ntiles) * a.wg_per_tile);
-    }
-#define B2M_FLOW_H(D_, TW_, WPB_, F_) conv_fwd_flow_kernel<D_, TW_, 0, WPB_, 1, F_><<<fo.grid, 64 * WPB_, 0, st>>>(a)
+    // (balanced runs: whole workgroups per tile, and here -- unlike the fp32 entry -- only layers with K > 1)
+    const unsigned fgrid = conv_xcd_plan(a, (int64_t)a.nstrips * nslice, wpb, (a.nstrips * nslice) % wpb == 0 && K > 1);
+#define B2M_FLOW_H(D_, TW_, WPB_, F_) conv_fwd_flow_kernel<D_, TW_, 0, WPB_, 1, F_><<<fgrid, 64 * WPB_, 0, st>>>(a)
     if (CK == 16) {
         if (wpb == 4) { if (TW == 4) B2M_FLOW_H(2, 4, 4, 2); else if (TW == 3) B2M_FLOW_H(2, 3, 4, 2); else B2M_FLOW_H(2, 2, 4, 2); }
         else { if (TW == 4) B2M_FLOW_H(2, 4, 1, 2); else if (TW == 3) B2M_FLOW_H(2, 3, 1, 2); else B2M_FLOW_H(2, 2, 1, 2); }
@@ -2376,91 +2365,46 @@ __global__ __launch_bounds__(256) void wgrad_narrow_kernel(const float* __restri
     }
 }
 
-template <int MI>
-static void launch_wgrad_nj(int NJ, dim3 grid, hipStream_t st, const WgradArgs& a) {
+// the kernel family of one (16*MI x 16*NJ) block shape
+template <int MI, int NJ>
+static void launch_wgrad_block(dim3 grid, hipStream_t st, const WgradArgs& a) {
     if (a.trh) {                     // half operands, complete blocks, 16-byte aligned rows: f16 MFMA
-        if (a.swap) {
-            switch (NJ) {
-                case 1: conv_wgrad_trh_kernel<MI, 1, 1><<<grid, 256, 0, st>>>(a); break;
-                case 2: conv_wgrad_trh_kernel<MI, 2, 1><<<grid, 256, 0, st>>>(a); break;
-                case 3: conv_wgrad_trh_kernel<MI, 3, 1><<<grid, 256, 0, st>>>(a); break;
-                default: conv_wgrad_trh_kernel<MI, 4, 1><<<grid, 256, 0, st>>>(a); break;
-            }
-        } else {
-            switch (NJ) {
-                case 1: conv_wgrad_trh_kernel<MI, 1, 0><<<grid, 256, 0, st>>>(a); break;
-                case 2: conv_wgrad_trh_kernel<MI, 2, 0><<<grid, 256, 0, st>>>(a); break;
-                case 3: conv_wgrad_trh_kernel<MI, 3, 0><<<grid, 256, 0, st>>>(a); break;
-                default: conv_wgrad_trh_kernel<MI, 4, 0><<<grid, 256, 0, st>>>(a); break;
-            }
-        }
+        if (a.swap) conv_wgrad_trh_kernel<MI, NJ, 1><<<grid, 256, 0, st>>>(a);
+        else conv_wgrad_trh_kernel<MI, NJ, 0><<<grid, 256, 0, st>>>(a);
         return;
     }
     if (a.pipe && a.half) {          // half operands: the flat-pipeline kernel with hipcc-tracked loads, both row-role forms
-        if (a.swap) {
-            switch (NJ) {
-                case 1: conv_wgrad_flow_h_kernel<MI, 1, 1><<<grid, 256, 0, st>>>(a); break;
-                case 2: conv_wgrad_flow_h_kernel<MI, 2, 1><<<grid, 256, 0, st>>>(a); break;
-                case 3: conv_wgrad_flow_h_kernel<MI, 3, 1><<<grid, 256, 0, st>>>(a); break;
-                default: conv_wgrad_flow_h_kernel<MI, 4, 1><<<grid, 256, 0, st>>>(a); break;
-            }
-        } else {
-            switch (NJ) {
-                case 1: conv_wgrad_flow_h_kernel<MI, 1, 0><<<grid, 256, 0, st>>>(a); break;
-                case 2: conv_wgrad_flow_h_kernel<MI, 2, 0><<<grid, 256, 0, st>>>(a); break;
-                case 3: conv_wgrad_flow_h_kernel<MI, 3, 0><<<grid, 256, 0, st>>>(a); break;
-                default: conv_wgrad_flow_h_kernel<MI, 4, 0><<<grid, 256, 0, st>>>(a); break;
-            }
-        }
+        if (a.swap) conv_wgrad_flow_h_kernel<MI, NJ, 1><<<grid, 256, 0, st>>>(a);
+        else conv_wgrad_flow_h_kernel<MI, NJ, 0><<<grid, 256, 0, st>>>(a);
         return;
     }
     if (a.pipe) {
         // hand-issued loads (B2M_WGRAD_HANDLOADS: 0 never, 1 the 48 x 48 and 64 x 64 blocks only, 2 every block of 2..4 x 2..4 sub-tiles)
-        if constexpr (MI >= 2) {
+        if constexpr (MI >= 2 && NJ >= 2) {
             // (real rulebooks only: an identity map has every pair of a tile but the last one's -- nothing to mask, and the
             // A/B says so: 128 -> 96 on 1.2 M rows 94.0 against 95.3 TFLOP/s)
-            if (a.rb_in && NJ >= 2 && (a.handloads >= 2 || (a.handloads == 1 && MI == NJ && MI >= 3))) {
-                const size_t xl = (size_t)env_flag("B2M_WGRAD_LDS", 0);      // diagnostic: extra LDS per workgroup caps the resident waves
-                if (a.swap) {
-                    switch (NJ) {
-                        case 2: conv_wgrad_flow_kernel<MI, 2, 1, 1><<<grid, 256, xl, st>>>(a); break;
-                        case 3: conv_wgrad_flow_kernel<MI, 3, 1, 1><<<grid, 256, xl, st>>>(a); break;
-                        default: conv_wgrad_flow_kernel<MI, 4, 1, 1><<<grid, 256, xl, st>>>(a); break;
-                    }
-                    return;
-                }
-                switch (NJ) {
-                    case 2: conv_wgrad_flow_kernel<MI, 2, 1><<<grid, 256, xl, st>>>(a); break;
-                    case 3: conv_wgrad_flow_kernel<MI, 3, 1><<<grid, 256, xl, st>>>(a); break;
-                    default: conv_wgrad_flow_kernel<MI, 4, 1><<<grid, 256, xl, st>>>(a); break;
-                }
+            if (a.rb_in && (a.handloads >= 2 || (a.handloads == 1 && MI == NJ && MI >= 3))) {
+                const size_t xl = (size_t)b2m_env_int("B2M_WGRAD_LDS", 0);      // diagnostic: extra LDS per workgroup caps the resident waves
+                if (a.swap) conv_wgrad_flow_kernel<MI, NJ, 1, 1><<<grid, 256, xl, st>>>(a);
+                else conv_wgrad_flow_kernel<MI, NJ, 1><<<grid, 256, xl, st>>>(a);
                 return;
             }
         }
         if (!a.swap) {          // (exchanged row roles exist in the hand-issued form and in the plain kernel below)
-            switch (NJ) {
-                case 1: conv_wgrad_flow_kernel<MI, 1><<<grid, 256, 0, st>>>(a); break;
-                case 2: conv_wgrad_flow_kernel<MI, 2><<<grid, 256, 0, st>>>(a); break;
-                case 3: conv_wgrad_flow_kernel<MI, 3><<<grid, 256, 0, st>>>(a); break;
-                default: conv_wgrad_flow_kernel<MI, 4><<<grid, 256, 0, st>>>(a); break;
-            }
+            conv_wgrad_flow_kernel<MI, NJ><<<grid, 256, 0, st>>>(a);
             return;
         }
     }
-    if (a.half) {
-        switch (NJ) {
-            case 1: conv_wgrad_kernel<MI, 1, 1><<<grid, 256, 0, st>>>(a); break;
-            case 2: conv_wgrad_kernel<MI, 2, 1><<<grid, 256, 0, st>>>(a); break;
-            case 3: conv_wgrad_kernel<MI, 3, 1><<<grid, 256, 0, st>>>(a); break;
-            default: conv_wgrad_kernel<MI, 4, 1><<<grid, 256, 0, st>>>(a); break;
-        }
-        return;
-    }
+    if (a.half) conv_wgrad_kernel<MI, NJ, 1><<<grid, 256, 0, st>>>(a);
+    else conv_wgrad_kernel<MI, NJ><<<grid, 256, 0, st>>>(a);
+}
+template <int MI>
+static void launch_wgrad_nj(int NJ, dim3 grid, hipStream_t st, const WgradArgs& a) {
     switch (NJ) {
-        case 1: conv_wgrad_kernel<MI, 1><<<grid, 256, 0, st>>>(a); break;
-        case 2: conv_wgrad_kernel<MI, 2><<<grid, 256, 0, st>>>(a); break;
-        case 3: conv_wgrad_kernel<MI, 3><<<grid, 256, 0, st>>>(a); break;
-        default: conv_wgrad_kernel<MI, 4><<<grid, 256, 0, st>>>(a); break;
+        case 1: launch_wgrad_block<MI, 1>(grid, st, a); break;
+        case 2: launch_wgrad_block<MI, 2>(grid, st, a); break;
+        case 3: launch_wgrad_block<MI, 3>(grid, st, a); break;
+        default: launch_wgrad_block<MI, 4>(grid, st, a); break;
     }
 }
 static void launch_wgrad(int MI, int NJ, dim3 grid, hipStream_t st, const WgradArgs& a) {
@@ -2471,8 +2415,6 @@ static void launch_wgrad(int MI, int NJ, dim3 grid, hipStream_t st, const WgradA
         default: launch_wgrad_nj<4>(NJ, grid, st, a); break;
     }
 }
-// tuning switches (A/B inside one process: tools/bench_conv.py); read once per process (b2m_reload_env re-reads them)
-static int env_flag(const char* name, int dflt) { return b2m_env_int(name, dflt); }
 static int pick_blk(int c) {      // 16-column sub-tiles per wave block
     // 64 channels: four 32x32 blocks keep all 4 waves of a workgroup busy and fit the pipelined kernel at full
     // occupancy (+27..35 % over one 64x64 block)
@@ -2540,7 +2482,7 @@ static int conv_wgrad_impl(const float* x, int64_t ldx, int32_t cin, int64_t n_i
     if (!zeros_addr) B2M_HIP(hipGetSymbolAddress((void**)&zeros_addr, HIP_SYMBOL(g_zeros)));
     a.zeros = zeros_addr;
     // 1x1 layer with few output channels (the heads' last layers): a plain reduction, see wgrad_narrow_kernel
-    if (!half && !tr && rb_in == nullptr && cout <= 32 && cout % 16 != 0 && cin <= 1024 && !workspace && n_in >= n_out && env_flag("B2M_WGRAD_NARROW", 1)) {
+    if (!half && !tr && rb_in == nullptr && cout <= 32 && cout % 16 != 0 && cin <= 1024 && !workspace && n_in >= n_out && b2m_env_int("B2M_WGRAD_NARROW", 1)) {
         const unsigned g = (unsigned)cdiv64(n_out, WGN_ROWS);
         if (cout <= 4) wgrad_narrow_kernel<4><<<g, 256, 0, st>>>(x, ldx, cin, dy, lddy, cout, n_out, dw, lddw);
         else if (cout <= 8) wgrad_narrow_kernel<8><<<g, 256, 0, st>>>(x, ldx, cin, dy, lddy, cout, n_out, dw, lddw);
@@ -2567,7 +2509,7 @@ static int conv_wgrad_impl(const float* x, int64_t ldx, int32_t cin, int64_t n_i
     // a quarter with it and keep 4)
     // (identity maps of a few hundred tiles -- the heads' 96 -> 96 layers on ~10 k segments: 8-tile chunks left 20 workgroups
     // on 256 CUs, 40 us per launch; one block's atomics per 2 tiles are nothing against that)
-    const int min_tiles = env_flag("B2M_WGRAD_MIN_TILES", (rb_in == nullptr && a.ntiles <= 1024) ? 2 : a.ntiles >= 32 ? 8 : 4);
+    const int min_tiles = b2m_env_int("B2M_WGRAD_MIN_TILES", (rb_in == nullptr && a.ntiles <= 1024) ? 2 : a.ntiles >= 32 ? 8 : 4);
     if (tpc < min_tiles) tpc = min_tiles;
     { const int mx = large ? 32 : 64; if (tpc > mx) tpc = mx; }
     // (half operands on the f16 MFMA, conv_wgrad_trh_kernel: a slot costs a quarter of its fp32 MFMA time, so a wave's fixed costs
@@ -2576,9 +2518,9 @@ static int conv_wgrad_impl(const float* x, int64_t ldx, int32_t cin, int64_t n_i
     // 256->256 125 -> 158; with fewer workgroups (level 3 128->128: 270) 95 -> 71, and the transposed maps lose: both keep 8.)
     if (half && !tr && rb_in != nullptr && !workspace && tpc < 16 && b2m_env_int("B2M_WGRAD_MIN_TILES", -1) < 0) {
         const int nblk_ = a.nmb * a.nnb;
-        const int kp_ = (nblk_ <= 2 && K >= 4 && env_flag("B2M_WGRAD_KPACK", 1)) ? 4 / nblk_ : 1;
+        const int kp_ = (nblk_ <= 2 && K >= 4 && b2m_env_int("B2M_WGRAD_KPACK", 1)) ? 4 / nblk_ : 1;
         const int64_t wgs16 = (int64_t)((K + kp_ - 1) / kp_) * ((nblk_ + 3) / 4) * cdiv64(a.ntiles, 16);
-        if (wgs16 >= 500 && env_flag("B2M_WGRAD_TRH", 1)) tpc = 16;
+        if (wgs16 >= 500 && b2m_env_int("B2M_WGRAD_TRH", 1)) tpc = 16;
     }
     // Deterministic mode (workspace given): at most B2M_WGRAD_DET_CHUNKS tile chunks, every chunk stores its partial
     // blocks plainly and a second kernel adds them up in chunk order -- no atomics, the same bits on every run.
@@ -2588,18 +2530,18 @@ static int conv_wgrad_impl(const float* x, int64_t ldx, int32_t cin, int64_t n_i
     a.nz = (a.nmb * a.nnb + 3) / 4;
     // layers with one or two blocks (32->32, the 6->32 stem, 32->96): 4 or 2 offsets per workgroup instead of idle waves
     const int nblocks = a.nmb * a.nnb;
-    a.kpack = (nblocks <= 2 && K >= 4 && env_flag("B2M_WGRAD_KPACK", 1)) ? 4 / nblocks : 1;
+    a.kpack = (nblocks <= 2 && K >= 4 && b2m_env_int("B2M_WGRAD_KPACK", 1)) ? 4 / nblocks : 1;
     a.kgroups = (K + a.kpack - 1) / a.kpack;
     a.nwg = (int64_t)a.kgroups * cdiv64(a.ntiles, tpc) * a.nz;
     B2M_CHECK_ARG(a.nwg < (1ll << 31) - 8, "too many workgroups");
     // work item = (k fastest, block group, tile chunk): a chunk of the XCD order = all offsets and blocks of
     // tile chunks of one eighth (contiguous)
-    const XcdOrder xo = xcd_order(a.nwg, env_flag("B2M_XCD", 1) ? (int64_t)(1 << 20) * a.kgroups * a.nz : 0);
+    const XcdOrder xo = xcd_order(a.nwg, b2m_env_int("B2M_XCD", 1) ? (int64_t)(1 << 20) * a.kgroups * a.nz : 0);
     a.xcd_per = xo.chunk;
     dim3 grid(xo.grid);
     // XCD runs of equal work (the tail of rb_cnt, b2m_rulebook_balance), each cut into tile chunks from its own start
     a.xcd_start = nullptr;
-    if (rb_cnt && !workspace && a.ntiles >= B2M_BALANCE_MIN_TILES && env_flag("B2M_XCD", 1) && env_flag("B2M_XCD_BALANCE", 1)) {
+    if (rb_cnt && !workspace && a.ntiles >= B2M_BALANCE_MIN_TILES && b2m_env_int("B2M_XCD", 1) && b2m_env_int("B2M_XCD_BALANCE", 1)) {
         a.xcd_start = rb_cnt + (int64_t)K * a.ntiles;
         grid = dim3((unsigned)(8 * a.kgroups * a.nz * cdiv64(B2M_XCD_CAP(a.ntiles), tpc)));
     }
@@ -2608,20 +2550,19 @@ static int conv_wgrad_impl(const float* x, int64_t ldx, int32_t cin, int64_t n_i
     // columns that are never written)
     // (b2m_conv_wgrad_tr: x has the n_out rows of the tiles, dy the n_in rows the pair lists name)
     const int64_t nx = tr ? n_out : n_in, ny = tr ? n_in : n_out;
-    a.fast32 = (ldx >= (int64_t)a.nmb * 16 * MI && lddy >= (int64_t)a.nnb * 16 * NJ && n_out < (1 << 24) && n_in < (1 << 24) &&
-                ldx < (1 << 22) && lddy < (1 << 22) && ny * lddy * esz < (1ll << 32) && nx * ldx * esz < (1ll << 32) &&
-                env_flag("B2M_WGRAD_FAST32", 1)) ? 1 : 0;
+    a.fast32 = (ldx >= (int64_t)a.nmb * 16 * MI && lddy >= (int64_t)a.nnb * 16 * NJ && addr32(nx, ldx, esz) && addr32(ny, lddy, esz) &&
+                b2m_env_int("B2M_WGRAD_FAST32", 1)) ? 1 : 0;
     // The flat-pipeline kernel for real rulebooks and 32-bit addressable operands.  Its MFMAs are asm statements the
     // compiler's hazard recogniser cannot see: a block with a single accumulator (MI = NJ = 1: consecutive MFMAs on the
     // same registers) stays on the plain kernel, where the builtin lets hipcc place whatever the dependence needs.
-    a.pipe = (a.fast32 && (rb_in != nullptr || (n_in >= n_out && env_flag("B2M_WGRAD_PIPE_IDENT", 1))) && MI * NJ >= 2 &&
-              !workspace && env_flag("B2M_WGRAD_PIPE", 1)) ? 1 : 0;
+    a.pipe = (a.fast32 && (rb_in != nullptr || (n_in >= n_out && b2m_env_int("B2M_WGRAD_PIPE_IDENT", 1))) && MI * NJ >= 2 &&
+              !workspace && b2m_env_int("B2M_WGRAD_PIPE", 1)) ? 1 : 0;
     // (diagnostics, tools/debug_wgrad_h22.py: half operands, blocks of at most four sub-tiles on the plain kernel)
-    if (half && MI * NJ <= 4 && env_flag("B2M_WGRAD_H_PIPE_SMALL", 1) == 0) a.pipe = 0;
-    a.handloads = env_flag("B2M_WGRAD_HANDLOADS", 2);
+    if (half && MI * NJ <= 4 && b2m_env_int("B2M_WGRAD_H_PIPE_SMALL", 1) == 0) a.pipe = 0;
+    a.handloads = b2m_env_int("B2M_WGRAD_HANDLOADS", 2);
     // half operands: the f16-MFMA kernel wherever its 16-byte row chunks exist (complete blocks, aligned rows, a real rulebook)
     a.trh = (half && a.fast32 && rb_in != nullptr && !workspace && cin % (16 * MI) == 0 && cout % (16 * NJ) == 0 &&
-             ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ldx % 8 == 0 && lddy % 8 == 0 && env_flag("B2M_WGRAD_TRH", 1)) ? 1 : 0;
+             ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ldx % 8 == 0 && lddy % 8 == 0 && b2m_env_int("B2M_WGRAD_TRH", 1)) ? 1 : 0;
     launch_wgrad(MI, NJ, grid, st, a);
     if (workspace) {
         const int nchunks = (int)cdiv64(a.ntiles, tpc);

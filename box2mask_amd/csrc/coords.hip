@@ -403,7 +403,7 @@ __device__ __forceinline__ void rulebook_runs(const int32_t* __restrict__ cost, 
     }
     __syncthreads();
     if (tid == 0) {
-        const int cap = (int)((ntiles * 5 + 31) / 32);     // B2M_XCD_CAP: 1.25 x an eighth, rounded up
+        const int cap = (int)B2M_XCD_CAP(ntiles);
         for (int x = 1; x < 8; ++x) {
             if (start[x] < start[x - 1]) start[x] = start[x - 1];
             if (start[x] > start[x - 1] + cap) start[x] = start[x - 1] + cap;
@@ -489,7 +489,6 @@ __global__ __launch_bounds__(1024) void rulebook_order_kernel(int32_t* __restric
         order[p] = t;
     }
 }
-static int coords_env(const char* name, int dflt) { return b2m_env_int(name, dflt); }
 extern "C" int64_t b2m_rulebook_cnt_size(int32_t K, int64_t n_out) {
     const int64_t ntiles = cdiv64(n_out, B2M_TILE);
     return (int64_t)K * ntiles + 16 + 2 * ntiles;

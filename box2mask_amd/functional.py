@@ -519,6 +519,24 @@ def join_side_streams():
         torch.cuda.current_stream(dev).wait_stream(st)
 
 
+def issue_wgrad(run, dy, x1, x2, dw):
+    """Runs `run()`, the weight-gradient launches of one layer (they read dy, x1 and x2 -- x2 may be None -- and add into dw):
+    on the side stream where wgrad_on_side_stream() says so, else inline.  The one place that keeps the side stream's rules."""
+    if not wgrad_on_side_stream():
+        run()
+        return
+    main, side = torch.cuda.current_stream(dy.device), _side_stream(dy.device)
+    side.wait_stream(main)                      # dy, x and the zeroed gradient slot are ready
+    with torch.cuda.stream(side):
+        run()
+    for t in (dy, x1, x2, dw):                  # the allocator must not hand these out again before the side stream is done
+        if t is not None:
+            t.record_stream(side)
+    if not _side['armed']:                      # once per backward pass: the main stream joins at its end
+        _side['armed'] = True
+        torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
+
+
 class _SparseConv(torch.autograd.Function):
     """Sparse convolution Y[o] = sum_k X[in_k(o)] W[k] (+bias).  [ME-mem] MinkowskiConvolution /
     MinkowskiConvolutionTranspose forward+backward (/root/reference/models/resnet.py:61-65,
@@ -588,23 +606,12 @@ class _SparseConv(torch.autograd.Function):
             if dw is None:
                 dw = torch.zeros_like(weight, dtype=torch.float32)
             dw3 = dw if weight.dim() == 3 else dw.unsqueeze(0)
-            if wgrad_on_side_stream():
-                main, side = torch.cuda.current_stream(dy.device), _side_stream(dy.device)
-                side.wait_stream(main)                      # dy, x and the zeroed gradient slot are ready
-                with torch.cuda.stream(side):
-                    wgrad_raw(x1, dy, ctx.rb_f, K, dw3, 0, c1)
-                    if x2 is not None:
-                        wgrad_raw(x2, dy, ctx.rb_f, K, dw3, c1, x2.shape[1])
-                for t in (dy, x1, x2, dw):                  # the allocator must not hand these out again before the side stream is done
-                    if t is not None:
-                        t.record_stream(side)
-                if not _side['armed']:
-                    _side['armed'] = True
-                    torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
-            else:
+
+            def run():
                 wgrad_raw(x1, dy, ctx.rb_f, K, dw3, 0, c1)
                 if x2 is not None:
                     wgrad_raw(x2, dy, ctx.rb_f, K, dw3, c1, x2.shape[1])
+            issue_wgrad(run, dy, x1, x2, dw)
         if bias is not None and ctx.needs_input_grad[3]:
             db = grad_slot(bias)
             if db is not None and db.shape == (1, cout):
@@ -675,16 +682,16 @@ def conv_passthrough() -> bool:
     return os.environ.get('B2M_CONV_PASSTHROUGH', '1') == '1'
 
 
-def sparse_conv(x1, x2, weight, bias, rb_f, rb_b, mirror, n_out, collect_stats=False, passthrough=False):
-    """collect_stats: the caller will batch-normalise the result in training mode; the per-tile column sums then ride
-    along on the returned tensor (attribute `_b2m_tile_stats`, read by batch_norm) when the kernel can provide them.
-    passthrough: returns (y, x1, x2) -- x1 / x2 as aliases of the inputs for every OTHER consumer of them, whose gradients
-    the data gradient of this convolution is then accumulated onto (see _SparseConv.forward); the inputs themselves when
-    no gradient is being recorded."""
-    holder = [] if (collect_stats and conv_tile_stats()) else None
+def apply_conv(fn, args, want_stats, passthrough):
+    """fn.apply(*args, holder, alias) for a convolution `autograd.Function` whose arguments begin with the two sources and end
+    with the tile-statistics holder and the pass-through flag (_SparseConv, half_train._ConvH): makes the holder where the caller
+    wants tile statistics, decides whether the inputs come back as aliases, hangs the statistics on the result and unpacks the
+    aliases -- what sparse_conv and half_train.conv document."""
+    x1, x2 = args[0], args[1]
+    holder = [] if want_stats else None
     alias = bool(passthrough) and torch.is_grad_enabled() and conv_passthrough() and \
         (x1.requires_grad or (x2 is not None and x2.requires_grad))
-    out = _SparseConv.apply(x1, x2, weight, bias, rb_f, rb_b, mirror, n_out, holder, alias)
+    out = fn.apply(*args, holder, alias)
     y = out[0] if alias else out
     if holder:
         y._b2m_tile_stats = holder[0]
@@ -693,6 +700,15 @@ def sparse_conv(x1, x2, weight, bias, rb_f, rb_b, mirror, n_out, collect_stats=F
     if not alias:
         return y, x1, x2
     return (y, out[1], out[2] if x2 is not None else None)
+
+
+def sparse_conv(x1, x2, weight, bias, rb_f, rb_b, mirror, n_out, collect_stats=False, passthrough=False):
+    """collect_stats: the caller will batch-normalise the result in training mode; the per-tile column sums then ride
+    along on the returned tensor (attribute `_b2m_tile_stats`, read by batch_norm) when the kernel can provide them.
+    passthrough: returns (y, x1, x2) -- x1 / x2 as aliases of the inputs for every OTHER consumer of them, whose gradients
+    the data gradient of this convolution is then accumulated onto (see _SparseConv.forward); the inputs themselves when
+    no gradient is being recorded."""
+    return apply_conv(_SparseConv, (x1, x2, weight, bias, rb_f, rb_b, mirror, n_out), collect_stats and conv_tile_stats(), passthrough)
 
 
 # ----------------------------------------------------------------------------- batch norm

@@ -261,19 +261,7 @@ class _ConvH(torch.autograd.Function):
                 _wgrad_h(x1, dy, ctx.rb_f, K, dw3, 0, inv)      # (inv: the kernel un-scales the block on its way into dW)
                 if x2 is not None:
                     _wgrad_h(x2, dy, ctx.rb_f, K, dw3, c1, inv)
-            if F_.wgrad_on_side_stream():
-                main, side = torch.cuda.current_stream(dy.device), F_._side_stream(dy.device)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    run()
-                for t in (dy, x1, x2, dw):
-                    if t is not None:
-                        t.record_stream(side)
-                if not F_._side['armed']:
-                    F_._side['armed'] = True
-                    torch.autograd.Variable._execution_engine.queue_callback(F_.join_side_streams)
-            else:
-                run()
+            F_.issue_wgrad(run, dy, x1, x2, dw)
         return dx1, dx2, dw, None, None, None, None, None, None
 
 
@@ -282,18 +270,7 @@ def conv(x1, x2, weight, rb_f, rb_b, mirror, n_out, collect_stats=False, passthr
     returned tensor (attribute `_b2m_tile_stats`, read by batch_norm), as functional.sparse_conv does for the fp32 layers.
     passthrough: returns (y, x1, x2) with x1 / x2 aliases of the inputs for every OTHER consumer of them (functional.sparse_conv);
     the inputs themselves when no gradient is being recorded."""
-    holder = [] if (collect_stats and conv_tile_stats()) else None
-    alias = bool(passthrough) and torch.is_grad_enabled() and F_.conv_passthrough() and \
-        (x1.requires_grad or (x2 is not None and x2.requires_grad))
-    out = _ConvH.apply(x1, x2, weight, rb_f, rb_b, mirror, n_out, holder, alias)
-    y = out[0] if alias else out
-    if holder:
-        y._b2m_tile_stats = holder[0]
-    if not passthrough:
-        return y
-    if not alias:
-        return y, x1, x2
-    return (y, out[1], out[2] if x2 is not None else None)
+    return F_.apply_conv(_ConvH, (x1, x2, weight, rb_f, rb_b, mirror, n_out), collect_stats and conv_tile_stats(), passthrough)
 
 
 _ws = {}
