@@ -636,7 +636,8 @@ __global__ void morton_keys_kernel(const int32_t* __restrict__ coords, int64_t n
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     i32x4 c = *(const i32x4*)(coords + i * 4);
-    // batch index in the top 15 bits (keys stay non-negative as int64), 3 x 16 interleaved coordinate bits below
+    // batch index in the top 16 bits, 3 x 16 interleaved coordinate bits below.  The key is an UNSIGNED 64-bit value: stored as
+    // int64 it is negative from batch index 32768 on, and b2m_radix_argsort orders the bit patterns as unsigned
     uint64_t k = ((uint64_t)(uint32_t)c.x << 48) | spread3((uint32_t)c.y) | (spread3((uint32_t)c.z) << 1) |
                  (spread3((uint32_t)c.w) << 2);
     keys[i] = (int64_t)k;

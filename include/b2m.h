@@ -50,7 +50,9 @@ int b2m_coords_build(const int32_t* coords, int64_t n, uint64_t* keys, int32_t* 
 /* Morton (Z-order) key per coordinate row: batch index in bits 48.., x/y/z bits interleaved below.  Sorting the rows
  * of a batch by this key before building the maps makes 64-row tiles spatially compact (denser rulebook groups,
  * fewer active offsets per tile, better L2 locality of the gathers); row order is otherwise free ([ME] gives no
- * order guarantee beyond input order, which the host restores at the boundary).  Requires b < 32768. */
+ * order guarantee beyond input order, which the host restores at the boundary).  The key is an unsigned 64-bit value in
+ * an int64 slot: negative as int64 from b = 32768 on (b <= 65534 is accepted), and b2m_radix_argsort orders keys as
+ * unsigned -- compare them as uint64, never as int64. */
 int b2m_morton_keys(const int32_t* coords, int64_t n, int64_t* keys, void* stream);
 /* Hilbert-curve key per coordinate row, same layout (batch index in bits 48.., 3 x `bits` index bits below; every coordinate
  * < 2^bits, bits <= 16): the default row order -- a curve without the Z-order's jumps gives more compact tiles (denser

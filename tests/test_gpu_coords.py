@@ -3,26 +3,9 @@ import numpy as np
 import pytest
 import torch
 
+from _coords_rule import _decode_rulebook, _expected_runs, _hilbert_keys_numpy, _morton_keys_numpy
+
 pytestmark = pytest.mark.gpu
-
-
-def _decode_rulebook(rb):
-    """tile rulebook -> neighbour table (K, n_out)."""
-    from box2mask_amd.sparse import TILE
-    K, n_out, nt = rb.K, rb.n_out, rb.ntiles
-    ldr = nt * TILE
-    rin = rb.rb_in[:K * ldr].cpu().numpy().reshape(K, nt, TILE)
-    rout = rb.rb_out[:K * ldr].cpu().numpy().reshape(K, nt, TILE)
-    cnt = rb.rb_cnt[:K * nt].cpu().numpy().reshape(K, nt)
-    nbr = np.full((K, nt * TILE), -1, np.int32)
-    for k in range(K):
-        for t in range(nt):
-            c = cnt[k, t]
-            assert (rin[k, t, c:] == -1).all() and (rout[k, t, c:] == 0).all()
-            o = rout[k, t, :c].astype(np.int64)
-            assert (np.diff(o) > 0).all()                      # compacted in output-row order
-            nbr[k, t * TILE + o] = rin[k, t, :c]
-    return nbr[:, :n_out], int(cnt.sum())
 
 
 def _check(coords, levels=4, k0=5):
@@ -121,25 +104,6 @@ def test_full_size_scene_properties():
     for l in range(7):
         tot = m.rulebook_down(l).pairs
         assert tot == m.n(l)                                          # every fine voxel is exactly one pair
-
-
-def _expected_runs(cnt):
-    """XCD work boundaries as include/b2m.h states them (rb_cnt tail), restated with numpy."""
-    K, nt = cnt.shape
-    cost = np.where(cnt > 0, 3 * ((cnt + 15) // 16) + 1, 0).sum(0).astype(np.int64)
-    prefix = np.cumsum(cost)
-    total = int(prefix[-1]) if nt else 0
-    start = [nt * x // 8 for x in range(8)] + [nt]
-    if total > 0:
-        for x in range(1, 8):
-            target = (total * x + 7) // 8
-            start[x] = int(np.searchsorted(prefix, target, side='left')) + 1
-    cap = (nt * 5 + 31) // 32
-    for x in range(1, 8):
-        start[x] = min(max(start[x], start[x - 1]), start[x - 1] + cap)
-    for x in range(7, 0, -1):
-        start[x] = max(start[x], start[x + 1] - cap)
-    return cost, np.array(start), cap
 
 
 @pytest.mark.parametrize('case', ['scene', 'skewed', 'tiny', 'empty_half'])
@@ -248,35 +212,6 @@ def test_radix_argsort_matches_stable_sort(n):
         assert torch.equal(inv.cpu()[ref], torch.arange(n)), what
 
 
-def _hilbert_keys_numpy(c, bits):
-    """Skilling's transform, vectorised (the restatement b2m_hilbert_keys is checked against)."""
-    X = c[:, 1:4].astype(np.uint64).copy()
-    M = np.uint64(1) << np.uint64(bits - 1)
-    Q = M
-    while Q > 1:
-        P = Q - np.uint64(1)
-        for a in range(3):
-            sel = (X[:, a] & Q) != 0
-            X[sel, 0] ^= P
-            ns = ~sel
-            t = (X[ns, 0] ^ X[ns, a]) & P
-            X[ns, 0] ^= t
-            X[ns, a] ^= t
-        Q >>= np.uint64(1)
-    X[:, 1] ^= X[:, 0]; X[:, 2] ^= X[:, 1]
-    t = np.zeros(len(X), np.uint64)
-    Q = M
-    while Q > 1:
-        t[(X[:, 2] & Q) != 0] ^= (Q - np.uint64(1))
-        Q >>= np.uint64(1)
-    X ^= t[:, None]
-    k = c[:, 0].astype(np.uint64) << np.uint64(48)
-    for bit in range(bits):
-        for a in range(3):
-            k |= ((X[:, a] >> np.uint64(bit)) & np.uint64(1)) << np.uint64(3 * bit + (2 - a))
-    return k.astype(np.int64)
-
-
 def test_hilbert_keys_walk_a_dense_cube_cell_by_cell_and_match_the_restatement():
     """(i) On a dense 16^3 cube the rows sorted by key form ONE path through face-adjacent cells -- the defining property of a
     Hilbert curve, independent of any implementation; (ii) random coordinates of two scenes: keys equal the numpy restatement
@@ -311,12 +246,7 @@ def test_row_order_switch_morton_keeps_the_z_order(monkeypatch):
     rng = np.random.default_rng(5)
     c = np.unique(np.concatenate([rng.integers(0, 2, (4000, 1)), rng.integers(0, 300, (4000, 3))], 1), axis=0).astype(np.int32)
 
-    def zkey(c):
-        k = c[:, 0].astype(np.uint64) << np.uint64(48)
-        for bit in range(16):
-            for a, sh in ((1, 0), (2, 1), (3, 2)):
-                k |= ((c[:, a].astype(np.uint64) >> np.uint64(bit)) & np.uint64(1)) << np.uint64(3 * bit + sh)
-        return k
+    zkey = _morton_keys_numpy
     monkeypatch.setenv('B2M_ROW_ORDER', 'morton')
     m = CoordinateManager(torch.from_numpy(c), reorder=True)
     assert np.array_equal(m.perm.cpu().numpy(), np.argsort(zkey(c), kind='stable'))
