@@ -225,10 +225,11 @@ __device__ __forceinline__ void nmc_scene(const float* __restrict__ boxes, int n
     const int tid = threadIdx.x;
     const bool in_lds = npad <= NMC_LDS_SORT;
 
-    // ---- visiting order: descending score, ties by ascending row
+    // ---- visiting order: descending score, ties by ascending row.  (s + 0.0f turns -0.0 into +0.0 -- the two zeros are EQUAL
+    // scores, but their bit patterns gave different keys: a +0.0 box was visited before a -0.0 box of a lower row)
     for (int j = tid; j < npad; j += NMC_THREADS) {
         uint64_t key = ~0ull;
-        if (j < n) key = ((uint64_t)f2ord_u(-boxes[(int64_t)j * 7]) << 32) | (uint32_t)j;
+        if (j < n) key = ((uint64_t)f2ord_u(-(boxes[(int64_t)j * 7] + 0.0f)) << 32) | (uint32_t)j;
         if (in_lds) skeys[j] = key; else order[j] = key;
     }
     for (int w = tid; w < (n + 31) / 32; w += NMC_THREADS) {
