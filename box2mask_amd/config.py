@@ -22,6 +22,9 @@ def scannet_config(**overrides):
         loss_weight_per_vox_semantics=1.0,
         mlp_bb_scores_start_epoch=100, mlp_center_scores_start_epoch=0,
         eval_ths=[0.5, 0.05, 0.3, 0.6],                                                    # configs/scannet.txt:15
+        # threshold search (config_loader.py:133-139): np.linspace triples, read by param_search.ThresholdGrid.from_cfg
+        cluster_th_search=[0.3, 0.8, 6], score_th_search=[0, 0.2, 5], mask_bin_th_search=[0.2, 0.35, 4],
+        mask_nms_th_search=[0.4, 0.8, 5],
         checkpoint_path='experiments/scannet/checkpoints/', voxel_size=0.02, batch_size=8, lr=1e-3,
         half_inference=False,        # build extension (no reference field): inference on half activations, see model.Model
         half_training=False,         # build extension: training passes with the trunk's activations / gradients in half (half_train.py)

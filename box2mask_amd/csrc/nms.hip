@@ -587,10 +587,11 @@ __global__ __launch_bounds__(256) void mask_project_batch_kernel(const MaskScene
         if (lane < nr) d.bits[(r0 + lane) * d.words + w] = mine;
     }
 }
-__global__ __launch_bounds__(256) void mask_inter_batch_kernel(const MaskScene* __restrict__ sc) {
+// (sweep: the table is wanted whatever field 10 says -- b2m_mask_nms_sweep_batch writes its flags elsewhere)
+__global__ __launch_bounds__(256) void mask_inter_batch_kernel(const MaskScene* __restrict__ sc, bool sweep) {
     const MaskScene d = sc[blockIdx.z];
     const int i = blockIdx.y, j = blockIdx.x, k = (int)d.ksel;
-    if (i >= k || j >= k || j < i || d.keep == nullptr) return;
+    if (i >= k || j >= k || j < i || (d.keep == nullptr && !sweep)) return;
     __shared__ int wsum[4];
     int s = 0;
     const uint64_t* a = d.bits + (int64_t)i * d.words;
@@ -606,12 +607,8 @@ __global__ __launch_bounds__(256) void mask_inter_batch_kernel(const MaskScene* 
         d.inter[(int64_t)j * k + i] = t;
     }
 }
-__global__ __launch_bounds__(256) void mask_greedy_batch_kernel(const MaskScene* __restrict__ sc, float th) {
-    const MaskScene d = sc[blockIdx.x];
-    const int k = (int)d.ksel;
-    if (d.keep == nullptr || k == 0) return;
-    int32_t* keep = d.keep;
-    const int32_t* inter = d.inter;
+// the greedy walk of one workgroup of 256 threads over a k x k intersection table: keep[] doubles as the alive flag
+__device__ __forceinline__ void mask_greedy_walk(const int32_t* __restrict__ inter, int k, float th, int32_t* __restrict__ keep) {
     for (int j = threadIdx.x; j < k; j += 256) keep[j] = 1;
     __syncthreads();
     for (int i = 0; i < k; ++i) {
@@ -627,6 +624,12 @@ __global__ __launch_bounds__(256) void mask_greedy_batch_kernel(const MaskScene*
         }
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(256) void mask_greedy_batch_kernel(const MaskScene* __restrict__ sc, float th) {
+    const MaskScene d = sc[blockIdx.x];
+    const int k = (int)d.ksel;
+    if (d.keep == nullptr || k == 0) return;
+    mask_greedy_walk(d.inter, k, th, d.keep);
 }
 // label histogram of a mask row.  A wave reads 64 consecutive words of the bit row at once (512 contiguous bytes) and then
 // works only on the non-zero ones, all 64 lanes on the 64 voxels of one word (a coalesced read of their labels): a thread
@@ -705,7 +708,7 @@ extern "C" int b2m_mask_nms_batch(const int64_t* desc, int32_t n_scenes, int32_t
     B2M_CHECK_ARG(n_scenes >= 0 && n_scenes <= 65535 && max_k >= 0 && max_k <= 65535, "bad sizes");
     if (n_scenes == 0 || max_k == 0) return B2M_OK;
     B2M_CHECK_ARG(desc, "NULL argument");
-    mask_inter_batch_kernel<<<dim3((unsigned)max_k, (unsigned)max_k, (unsigned)n_scenes), 256, 0, st>>>((const MaskScene*)desc);
+    mask_inter_batch_kernel<<<dim3((unsigned)max_k, (unsigned)max_k, (unsigned)n_scenes), 256, 0, st>>>((const MaskScene*)desc, false);
     mask_greedy_batch_kernel<<<(unsigned)n_scenes, 256, 0, st>>>((const MaskScene*)desc, th);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
@@ -809,6 +812,162 @@ extern "C" int b2m_mask_gather_batch(const int64_t* desc, int32_t n_scenes, int6
     B2M_CHECK_ARG(desc, "NULL argument");
     mask_gather_batch_kernel<<<dim3((unsigned)cdiv64(max_pts, 1024), (unsigned)n_scenes), 256, 0, (hipStream_t)stream>>>(
         (const MaskScene*)desc);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+
+// ------------------------------------------------------------------ threshold sweep (box2mask_amd/param_search.py)
+// Evaluater.param_search (/root/reference/models/evaluation.py:353-366) evaluates every mask_nms_th of its grid as a job of its
+// own.  The intersection table does not depend on the threshold: it is built once, and workgroup (scene, t) walks it for ths[t].
+// Row t is what b2m_mask_nms / b2m_mask_nms_batch write for th = ths[t]: the same division, the same `!(iou <= th)`.
+struct SweepThs { float th[B2M_SWEEP_MAX_TH]; };
+__global__ __launch_bounds__(256) void mask_greedy_sweep_kernel(const int32_t* __restrict__ inter, int k, SweepThs ths,
+                                                                int32_t* __restrict__ keep) {
+    mask_greedy_walk(inter, k, ths.th[blockIdx.x], keep + (int64_t)blockIdx.x * k);
+}
+__global__ __launch_bounds__(256) void mask_greedy_sweep_batch_kernel(const MaskScene* __restrict__ sc, SweepThs ths,
+                                                                      int32_t* __restrict__ keep, int64_t total_sel) {
+    const MaskScene d = sc[blockIdx.x];
+    const int k = (int)d.ksel;
+    if (k == 0) return;
+    mask_greedy_walk(d.inter, k, ths.th[blockIdx.y], keep + (int64_t)blockIdx.y * total_sel + d.row0_sel);
+}
+static int sweep_ths(const float* ths_host, int32_t n_th, SweepThs& t) {
+    B2M_CHECK_ARG(ths_host && n_th >= 1 && n_th <= B2M_SWEEP_MAX_TH, "1 <= n_th <= 64 thresholds, given on the host");
+    for (int i = 0; i < n_th; ++i) t.th[i] = ths_host[i];
+    return B2M_OK;
+}
+extern "C" int b2m_mask_nms_sweep(const uint64_t* bits, int32_t k, int64_t words, const float* ths_host, int32_t n_th,
+                                  int32_t* inter, int32_t* keep, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SweepThs t{};
+    if (int rc = sweep_ths(ths_host, n_th, t)) return rc;
+    B2M_CHECK_ARG(k >= 0 && k <= 65535 && words >= 0, "bad sizes");
+    if (k == 0) return B2M_OK;
+    B2M_CHECK_ARG(bits && inter && keep, "NULL argument");
+    mask_inter_kernel<<<dim3((unsigned)k, (unsigned)k), 256, 0, st>>>(bits, k, words, inter);
+    mask_greedy_sweep_kernel<<<(unsigned)n_th, 256, 0, st>>>(inter, k, t, keep);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+extern "C" int b2m_mask_nms_sweep_batch(const int64_t* desc, int32_t n_scenes, int32_t max_k, const float* ths_host, int32_t n_th,
+                                        int32_t* keep, int64_t total_sel, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SweepThs t{};
+    if (int rc = sweep_ths(ths_host, n_th, t)) return rc;
+    B2M_CHECK_ARG(n_scenes >= 0 && n_scenes <= 65535 && max_k >= 0 && max_k <= 65535 && total_sel >= 0, "bad sizes");
+    if (n_scenes == 0 || max_k == 0 || total_sel == 0) return B2M_OK;
+    B2M_CHECK_ARG(desc && keep, "NULL argument");
+    mask_inter_batch_kernel<<<dim3((unsigned)max_k, (unsigned)max_k, (unsigned)n_scenes), 256, 0, st>>>((const MaskScene*)desc, true);
+    mask_greedy_sweep_batch_kernel<<<dim3((unsigned)n_scenes, (unsigned)n_th), 256, 0, st>>>((const MaskScene*)desc, t, keep, total_sel);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+
+// ------------------------------------------------------------------ label histogram of every mask row THROUGH an index
+// hist[r][c] = |{p < n_pts : bit index[p] of row r set and label[p] == c}|: the prediction x ground-truth counts of
+// assign_instances_for_scan on the scene's POINTS, from masks that live on voxels -- b2m_mask_gather, b2m_mask_pack and
+// b2m_mask_hist without the k x n_pts bytes in between.  As b2m_mask_gather_batch_t: a voxel-major image first (word c of voxel v =
+// rows 64c .. 64c + 63 at v), then one 8-byte look-up per point and 64 rows; every set bit is one integer atomic on the table in
+// global memory (k x n_class does not fit LDS at the caps: 65535 x 2048).  Integer sums: the same bits on every run.
+struct HistScene {
+    const uint64_t* bits; int64_t k; int64_t words; int64_t n_vox; const int64_t* index; const int32_t* label; int64_t n_pts;
+    int64_t n_class; uint64_t* tbits; int32_t* hist;
+};
+static_assert(sizeof(HistScene) == B2M_HIST_DESC * 8, "HistScene must match B2M_HIST_DESC");
+// block bx of a scene: zero its share of the table, then transpose the four 64-voxel words it owns
+__device__ __forceinline__ void hist_prepare(const HistScene& d, int64_t bx, int64_t nbx) {
+    const int64_t cells = d.k * d.n_class;
+    for (int64_t e = bx * 256 + threadIdx.x; e < cells; e += nbx * 256) d.hist[e] = 0;
+    const int64_t w = bx * 4 + (threadIdx.x >> 6);
+    if (w >= d.words) return;
+    const int lane = lane_id();
+    const int nw = (int)((d.k + 63) >> 6);
+    const int64_t v = w * 64 + lane;
+    for (int c = 0; c < nw; ++c) {
+        const int64_t r = (int64_t)c * 64 + lane;                          // lane r: word w of row r
+        const uint64_t mine = r < d.k ? d.bits[r * d.words + w] : 0ull;
+        uint64_t out = 0;                                                  // lane j: bit r = bit j of lane r's word
+#pragma unroll 8
+        for (int j = 0; j < 64; ++j) {
+            const uint64_t m = __ballot((mine >> j) & 1ull);
+            if (lane == j) out = m;
+        }
+        if (v < d.n_vox) d.tbits[v * nw + c] = out;
+    }
+}
+// A wave owns 64 consecutive points.  Neighbouring points mostly lie in the same masks and the same ground-truth instance, so their
+// adds meet in ONE cell: lane by lane that is 64 atomics on one address (the first form of this kernel: 7.3 ms per launch on 8
+// scenes of 1.2 M points, every workgroup queueing on a few hundred cells).  The lanes take their set bits in step; the cells of a
+// step are merged inside the wave -- a leader per distinct cell adds the number of lanes that named it.  The whole wave stays in
+// the loops (the ballots need every lane); a lane without work carries cell -1.
+__device__ __forceinline__ void hist_count(const HistScene& d, int64_t p) {
+    const int lane = lane_id();
+    bool ok = p < d.n_pts;
+    int c = -1;
+    int64_t v = 0;
+    if (ok) { c = d.label[p]; ok = c >= 0 && c < d.n_class; }
+    if (ok) { v = d.index ? d.index[p] : p; ok = v >= 0 && v < d.n_vox; }   // (a point that names no voxel lies in no mask)
+    if (!__ballot(ok)) return;
+    const int nw = (int)((d.k + 63) >> 6);
+    for (int cw = 0; cw < nw; ++cw) {
+        uint64_t t = ok ? d.tbits[v * nw + cw] : 0ull;
+        while (__ballot(t != 0ull)) {
+            int cell = -1;                                                  // k * n_class <= 65535 * 2048 < 2^31
+            if (t) {
+                cell = (cw * 64 + __builtin_ctzll(t)) * (int)d.n_class + c;
+                t &= t - 1;
+            }
+            uint64_t todo = __ballot(cell >= 0);
+            while (todo) {
+                const int leader = __builtin_ctzll(todo);
+                const int cell0 = __shfl(cell, leader, 64);
+                const uint64_t same = __ballot(cell == cell0);
+                if (lane == leader) atomicAdd(d.hist + cell0, __popcll(same));
+                todo &= ~same;
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void hist_prepare_kernel(HistScene d) { hist_prepare(d, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void hist_count_kernel(HistScene d) { hist_count(d, (int64_t)blockIdx.x * 256 + threadIdx.x); }
+__global__ __launch_bounds__(256) void hist_prepare_batch_kernel(const HistScene* __restrict__ sc) {
+    const HistScene d = sc[blockIdx.y];
+    if (d.k == 0) return;
+    hist_prepare(d, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(256) void hist_count_batch_kernel(const HistScene* __restrict__ sc) {
+    const HistScene d = sc[blockIdx.y];
+    if (d.k == 0) return;
+    hist_count(d, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+extern "C" int b2m_mask_hist_index(const uint64_t* bits, int64_t words, int32_t k, int64_t n_vox, const int64_t* index,
+                                   const int32_t* label, int64_t n_pts, int32_t n_class, uint64_t* tbits, int32_t* hist,
+                                   void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(k >= 0 && k <= 65535 && n_class >= 1 && n_class <= HIST_MAX, "bad sizes (k <= 65535, n_class <= 2048)");
+    B2M_CHECK_ARG(n_vox >= 0 && words == cdiv64(n_vox, 64) && n_pts >= 0 && n_pts <= 0x7FFFFFFF, "bad sizes (words = ceil(n_vox / 64))");
+    if (k == 0) return B2M_OK;
+    B2M_CHECK_ARG(hist && (n_pts == 0 || label) && (words == 0 || (bits && tbits)), "NULL argument");
+    HistScene d{bits, k, words, n_vox, index, label, n_pts, n_class, tbits, hist};
+    int64_t nb = cdiv64(words, 4), nz = cdiv64((int64_t)k * n_class, 256);   // blocks of the transposition / of the zero fill
+    if (nz > 1024) nz = 1024;                                                // (a block strides over the table)
+    if (nb < nz) nb = nz;
+    hist_prepare_kernel<<<(unsigned)nb, 256, 0, st>>>(d);
+    if (n_pts > 0 && words > 0) hist_count_kernel<<<(unsigned)cdiv64(n_pts, 256), 256, 0, st>>>(d);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+extern "C" int b2m_mask_hist_index_batch(const int64_t* desc, int32_t n_scenes, int64_t max_words, int64_t max_pts, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(n_scenes >= 0 && n_scenes <= 65535 && max_words >= 0 && max_pts >= 0 && max_pts <= 0x7FFFFFFF, "bad sizes");
+    if (n_scenes == 0) return B2M_OK;
+    B2M_CHECK_ARG(desc, "NULL argument");
+    int64_t nb = cdiv64(max_words, 4);
+    if (nb < 256) nb = 256;                                                // (enough blocks for the zero fill of a small scene)
+    hist_prepare_batch_kernel<<<dim3((unsigned)nb, (unsigned)n_scenes), 256, 0, st>>>((const HistScene*)desc);
+    if (max_pts > 0 && max_words > 0)
+        hist_count_batch_kernel<<<dim3((unsigned)cdiv64(max_pts, 256), (unsigned)n_scenes), 256, 0, st>>>((const HistScene*)desc);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }

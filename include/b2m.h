@@ -603,6 +603,41 @@ int b2m_mask_gather_batch(const int64_t* desc, int32_t n_scenes, int64_t total_k
 int b2m_mask_gather_batch_t(const int64_t* desc, int32_t n_scenes, int64_t total_kept, int64_t max_pts, int64_t max_words,
                             const int64_t* tbits, void* stream);
 
+/* ---- threshold sweep (box2mask_amd/param_search.py; Evaluater.param_search, models/evaluation.py:353-366, runs every setting
+ * of its grid as a job of its own).
+ *
+ * b2m_mask_nms for n_th thresholds at once: the k x k intersection table is built ONCE, then one workgroup per threshold walks
+ * it.  keep: int32[n_th][k]; row t holds exactly the flags b2m_mask_nms writes for th = ths_host[t] (the same float32
+ * inter / union, the same `!(iou <= th)`).  ths_host: n_th floats in HOST memory, 1 <= n_th <= B2M_SWEEP_MAX_TH (they travel as a
+ * kernel argument).  inter: int32[k*k], left filled. */
+#define B2M_SWEEP_MAX_TH 64
+int b2m_mask_nms_sweep(const uint64_t* bits, int32_t k, int64_t words, const float* ths_host, int32_t n_th,
+                       int32_t* inter, int32_t* keep, void* stream);
+/* The same for every scene of a B2M_MASK_DESC table.  Reads fields 3 (ksel), 7 (bits), 8 (words), 9 (inter) and 18 (first global
+ * row of the scene) with their meaning above; field 10 is neither read nor written.  keep: int32[n_th][total_sel], total_sel = the
+ * sum of ksel; the flags of scene s for threshold t start at keep[t * total_sel + field 18 of s] and are what
+ * b2m_mask_nms_batch writes for that scene with th = ths_host[t].  A scene with ksel = 0 writes nothing. */
+int b2m_mask_nms_sweep_batch(const int64_t* desc, int32_t n_scenes, int32_t max_k, const float* ths_host, int32_t n_th,
+                             int32_t* keep, int64_t total_sel, void* stream);
+
+/* hist[r*n_class + c] = |{p < n_pts : bit index[p] of bit row r is set and label[p] == c}| for every one of the k rows: the
+ * prediction x ground-truth counts of assign_instances_for_scan (utils/eval_metric.py:316-330) on the scene's POINTS from masks
+ * that live on its voxels (index = vox2point, models/detection_net.py:469-471).  By definition b2m_mask_gather, then b2m_mask_pack,
+ * then b2m_mask_hist -- without the k x n_pts bytes.  bits: k x words with words = ceil(n_vox / 64) (bits at or above n_vox are
+ * ignored); index: int64[n_pts] with values in [0, n_vox), repeats allowed, voxels no point names allowed, NULL = identity (a
+ * point whose index lies outside [0, n_vox) is in no mask); labels outside [0, n_class) are skipped; n_class <= 2048, k <= 65535.
+ * tbits: scratch of n_vox * ceil(k / 64) uint64 (the voxel-major image of b2m_mask_gather_batch_t).  hist is zeroed here.  Integer
+ * atomics only: the same bits on every run. */
+int b2m_mask_hist_index(const uint64_t* bits, int64_t words, int32_t k, int64_t n_vox, const int64_t* index,
+                        const int32_t* label, int64_t n_pts, int32_t n_class, uint64_t* tbits, int32_t* hist, void* stream);
+/* The same for n_scenes scenes in two launches.  `desc`: device array of n_scenes records of B2M_HIST_DESC int64 fields (pointers
+ * stored as integers), the arguments of b2m_mask_hist_index in this order:
+ *    0 bits   1 k   2 words   3 n_vox   4 index   5 label   6 n_pts   7 n_class   8 tbits   9 hist
+ * The caller keeps every record within the limits above (they are device memory; only the two maxima are checked here).
+ * max_words / max_pts = the largest words / n_pts of the table. */
+#define B2M_HIST_DESC 10
+int b2m_mask_hist_index_batch(const int64_t* desc, int32_t n_scenes, int64_t max_words, int64_t max_pts, void* stream);
+
 /* ---------------------------------------------------------------- detection boxes (ARKitScenes oriented-box mAP)
  * The device half of Evaluater.arkitscenes_eval (models/evaluation.py:245-316): a prism per predicted mask (convex hull of the
  * mask's points in x-y, extruded over their z range, :280-292), the corners of every ground-truth box (utils/box_util.py:360-384)

@@ -1,0 +1,121 @@
+"""The threshold sweep (box2mask_amd/param_search.py) on ScanNet-shaped inputs, beside the same settings through the single-setting
+path: scenes of ~150 k voxels from synth.make_batch, votes as bench.py's votes leg makes them (every segment votes for its object's
+box with 2.5 cm noise, score logits ~ N(0, 2)), the default 6 x 5 x 4 x 5 grid.
+
+    python tools/bench_param_sweep.py [--scenes 8] [--voxels 150000] [--loop-settings 12]
+
+Reports the device ms of the sweep's stages (HIP events round every launch, a pass of its own: the events serialise the stream),
+the wall time of the sweep up to the tables, the wall time of the host matching of all settings, and the looped path --
+Model.pred2mask + eval_metric.compute_eval per setting -- timed on `--loop-settings` settings spread evenly over the grid and
+scaled to the grid (0 = every setting).  The looped settings' APs are compared with the sweep's.  One JSON line at the end.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import warnings
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from bench import synthetic_votes                                  # noqa: E402
+from box2mask_amd import _lib, eval_metric, param_search, synth   # noqa: E402
+from box2mask_amd.config import scannet_config                    # noqa: E402
+from box2mask_amd.model import Model                              # noqa: E402
+
+STAGES = ('b2m_nmc_batch', 'b2m_mask_project_batch', 'b2m_mask_nms_sweep_batch', 'b2m_label_hist_batch', 'b2m_mask_hist_index_batch')
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--scenes', type=int, default=8)
+    ap.add_argument('--voxels', type=int, default=150000)
+    ap.add_argument('--loop-settings', type=int, default=12, help='settings the looped path is timed on, scaled to the grid (0 = all)')
+    args = ap.parse_args(argv)
+    cfg = scannet_config()
+    model = Model(cfg, *synth.scannet_tables())
+    model.eval()
+    batch = synth.make_batch(args.scenes, seed0=0, target_voxels=args.voxels)
+    pred, _ = synthetic_votes(batch, cfg)
+    gts = {sc['name']: synth.gt_instance_ids(batch, b) for b, sc in enumerate(batch['scene'])}
+    grid = param_search.ThresholdGrid.from_cfg(cfg)
+    n_set = int(np.prod(grid.shape))
+    note = lambda msg: print('[bench_param_sweep] ' + msg, file=sys.stderr, flush=True)
+    note('%d scenes, %d voxels, %d settings' % (args.scenes, batch['vox_coords'].shape[0], n_set))
+    model.pred2mask_sweep(batch, pred, grid, gts)                                       # warm-up
+    tabs, sweep_s = wall(lambda: model.pred2mask_sweep(batch, pred, grid, gts))
+    # device time per stage
+    rec = []
+
+    def hook(name, a, meta=None):
+        if name not in STAGES:
+            return None
+        s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s_.record()
+
+        def done():
+            e_.record()
+            rec.append((name, s_, e_))
+        return done
+    _lib.set_hook(hook)
+    model.pred2mask_sweep(batch, pred, grid, gts)
+    torch.cuda.synchronize()
+    _lib.set_hook(None)
+    stages = {n: {'launches': 0, 'ms': 0.0} for n in STAGES}
+    for name, s_, e_ in rec:
+        stages[name]['launches'] += 1
+        stages[name]['ms'] += s_.elapsed_time(e_)
+    note('sweep %.3f s; matching every setting ...' % sweep_s)
+    # the whole search: sweep + records + matching of every setting
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)
+        res, search_s = wall(lambda: param_search.scannet_param_search(model, [(batch, pred)], gts, grid))
+    note('search %.1f s; the looped path ...' % search_s)
+    # the looped path on a subset
+    settings = list(grid.settings())
+    n_loop = n_set if args.loop_settings <= 0 else min(args.loop_settings, n_set)
+    chosen = [settings[i] for i in np.unique(np.linspace(0, n_set - 1, n_loop).round().astype(int))]
+    saved, agree = cfg.eval_ths, True
+    model.cfg.eval_ths = grid.eval_ths(*chosen[0])
+    eval_metric.compute_eval(model.pred2mask(batch, pred, 'eval'), gts)                  # warm-up
+    t_mask = t_eval = 0.0
+    for st in chosen:
+        model.cfg.eval_ths = grid.eval_ths(*st)
+        r, dt = wall(lambda: model.pred2mask(batch, pred, 'eval'))
+        t_mask += dt
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)
+            (avg, _), dt = wall(lambda: eval_metric.compute_eval(r, gts))
+        t_eval += dt
+        agree &= bool(np.array_equal(res['ap'][st], [avg['all_ap'], avg['all_ap_50%'], avg['all_ap_25%']], equal_nan=True))
+    model.cfg.eval_ths = saved
+    scale = n_set / len(chosen)
+    out = {'scenes': args.scenes, 'voxels': int(batch['vox_coords'].shape[0]), 'points': int(sum(t.n_pts for t in tabs)),
+           'segments': int(batch['input_location'].shape[0]), 'grid': list(grid.shape), 'settings': n_set,
+           'clusters_per_cluster_th': [int(sum(t.clusters[ci]['K'] for t in tabs)) for ci in range(grid.shape[0])],
+           'projected_rows_per_cluster_th': [int(sum(t.clusters[ci]['ks'][0] for t in tabs)) for ci in range(grid.shape[0])],
+           'stages': {n: {'launches': v['launches'], 'ms': round(v['ms'], 3)} for n, v in stages.items()},
+           'stages_device_ms': round(sum(v['ms'] for v in stages.values()), 3),
+           'sweep_wall_s': round(sweep_s, 4), 'search_wall_s': round(search_s, 3),
+           'host_matching_s': round(search_s - sweep_s, 3), 'distinct_record_sets_matched': res['n_evaluated'],
+           'best': res['best_ths'], 'best_ap_ap50_ap25': [float(v) for v in res['ap'][res['best']]],
+           'looped_settings_timed': len(chosen), 'looped_pred2mask_s': round(t_mask, 3), 'looped_compute_eval_s': round(t_eval, 3),
+           'looped_scaled_to_grid_s': round((t_mask + t_eval) * scale, 1), 'looped_is_scaled': len(chosen) != n_set,
+           'looped_ap_equals_sweep_ap': agree}
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

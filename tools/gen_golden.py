@@ -211,6 +211,107 @@ def gen_detection2mask():
     print('detection2mask.npz: %d arrays' % len(out))
 
 
+SWEEP_GRID = ([0.3, 0.5, 0.7], [0.0, 0.05, 0.2], [0.2, 0.35], [0.4, 0.8])
+SWEEP_WITH_MASKS = ((0, 0, 0, 1), (2, 2, 1, 0))
+
+
+def mask_content_sums(masks):
+    """64-bit content sum of every boolean row: the sum over its set points p of (p + 1) * 0x9E3779B97F4A7C15, modulo 2^64."""
+    masks = np.asarray(masks, bool)
+    w = (np.arange(1, masks.shape[1] + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15))
+    return np.array([w[m].sum(dtype=np.uint64) for m in masks], np.uint64).reshape(len(masks))
+
+
+def gen_sweep():
+    """tests/golden/param_sweep.npz: a 3 x 3 x 2 x 2 threshold grid, every setting run through the real SelectionNet.detection2mask
+    (the stubs of gen_detection2mask) and scored with the real utils/eval_metric.py (assign_instances_for_scan, evaluate_matches,
+    compute_averages; the ground truth of synth.gt_instance_ids in a temporary txt file as in gen_eval).  Per setting and scene the
+    scores, labels, point counts and content sums of the masks -- the masks themselves for two settings only, which keeps the
+    file small."""
+    import itertools
+    import tempfile
+    _install_stubs()
+    for a, t in (('float', float), ('bool', bool), ('int', int)):
+        if not hasattr(np, a):
+            setattr(np, a, t)
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    import models.detection_net as dn
+    import utils.eval_metric as E
+    valid, id2idx, _, is_fg = synth.scannet_tables()
+    cfg = SimpleNamespace(mlp_per_vox_semantics='mlp_per_vox_semantics', mlp_semantics='mlp_semantics',
+                          network_heads=['mlp_offsets', 'mlp_bounds', 'mlp_bb_scores', 'mlp_semantics'],
+                          do_segment_pooling=True)
+    ns = SimpleNamespace(requires_voxel_outputs=False, semantic_valid_class_ids=valid, is_foreground=is_fg)
+    batch, pred = _scene_inputs(11)
+    names = [s['name'] for s in batch['scene']]
+    out = {'sw_names': np.asarray(names), 'sw_input_location': batch['input_location'].numpy(), 'sw_batch_ids': batch['batch_ids'].numpy()}
+    for k, v in zip(('cluster_th', 'score_th', 'mask_bin_th', 'mask_nms_th'), SWEEP_GRID):
+        out['sw_' + k] = np.asarray(v, np.float64)
+    for k, v in pred.items():
+        out['sw_pred_' + k] = v.numpy()
+    gt_files = []
+    for si in range(len(names)):
+        out['sw_seg2vox%d' % si] = np.asarray(batch['seg2vox'][si])
+        out['sw_vox2point%d' % si] = np.asarray(batch['vox2point'][si])
+        gt = synth.gt_instance_ids(batch, si)
+        out['sw_gt_ids%d' % si] = gt
+        with tempfile.NamedTemporaryFile('w', suffix='.txt', delete=False) as f:
+            f.write('\n'.join(str(int(v)) for v in gt) + '\n')
+        gt_files.append(f.name)
+    shape = tuple(len(a) for a in SWEEP_GRID)
+    counts = np.zeros(shape + (len(names),), np.int64)
+    triples = set()
+
+    def run(ths, tag, with_masks):
+        """One setting through the reference; returns the instance count of every scene."""
+        res = dn.SelectionNet.detection2mask(ns, batch, {k: v.clone() for k, v in pred.items()}, cfg, 'eval', True, *ths)
+        matches, n_inst = {}, []
+        for si, name in enumerate(names):
+            r = res[name]
+            mask = r['mask'].numpy()
+            pre = 'sw_%s_s%d_' % (tag, si)
+            out[pre + 'conf'] = r['conf'].numpy()
+            out[pre + 'label_id'] = np.asarray(r['label_id'])
+            out[pre + 'count'] = mask.sum(1).astype(np.int64)
+            out[pre + 'sum'] = mask_content_sums(mask)
+            if with_masks:
+                out[pre + 'mask'] = np.packbits(mask, axis=1)
+            n_inst.append(mask.shape[0])
+            info = {'conf': r['conf'].numpy(), 'label_id': np.asarray(r['label_id']), 'mask': mask}
+            gt2pred, pred2gt = E.assign_instances_for_scan(name, info, gt_files[si])
+            matches[name] = {'gt': gt2pred, 'pred': pred2gt}
+        ap, _ = E.evaluate_matches(matches)
+        avgs = E.compute_averages(ap)
+        out['sw_%s_ap' % tag] = ap
+        out['sw_%s_avg' % tag] = np.array([avgs['all_ap'], avgs['all_ap_50%'], avgs['all_ap_25%']])
+        return n_inst
+
+    for q, st in enumerate(itertools.product(*(range(n) for n in shape))):
+        counts[st] = run([SWEEP_GRID[a][i] for a, i in enumerate(st)], 'q%02d' % q, st in SWEEP_WITH_MASKS)
+        triples.add(tuple(out['sw_q%02d_avg' % q].tolist()))
+    # one setting more, off the grid: score_th EQUAL to the score of an instance the grid keeps -- `scores > score_th` drops that
+    # cluster, `>=` would keep it (no score of these inputs equals a grid value, so the grid alone cannot tell the two apart)
+    q_tie = int(np.ravel_multi_index((1, 0, 0, 1), shape))
+    conf0 = out['sw_q%02d_s0_conf' % q_tie]
+    tie = float(conf0[len(conf0) // 2])
+    out['sw_tie_ths'] = np.array([SWEEP_GRID[0][1], tie, SWEEP_GRID[2][0], SWEEP_GRID[3][1]], np.float64)
+    n_tie = run(out['sw_tie_ths'].tolist(), 'tie', False)
+    assert np.float32(tie) == conf0[len(conf0) // 2] and n_tie[0] < len(conf0) and (out['sw_tie_s0_conf'] > np.float32(tie)).all()
+    for f in gt_files:
+        os.unlink(f)
+    # the fixture must never go flat: every axis changes the instance count of some scene, and the AP moves
+    for axis in range(4):
+        assert (np.diff(counts, axis=axis) != 0).any(), 'axis %d never changes an instance count' % axis
+    assert len(triples) >= 8, 'only %d distinct AP / AP50 / AP25 triples' % len(triples)
+    path = os.path.join(OUT, 'param_sweep.npz')
+    _savez_fixed(path, out)
+    assert os.path.getsize(path) <= 1000000
+    print('param_sweep.npz: %d bytes, %d settings, %d distinct (K0, K1), %d distinct AP triples, instances %s .. %s'
+          % (os.path.getsize(path), counts[..., 0].size, len({tuple(c) for c in counts.reshape(-1, len(names)).tolist()}),
+             len(triples), counts.reshape(-1, len(names)).min(0).tolist(), counts.reshape(-1, len(names)).max(0).tolist()))
+
+
 def gen_detection2mask_nopool():
     """SelectionNet.detection2mask with cfg.do_segment_pooling = False (detection_net.py:436-445: the heat-maps are NOT
     projected through seg2vox, the predictions already live on the voxels).  The reference's branch only executes when every
@@ -1450,7 +1551,9 @@ if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
     which = sys.argv[1:] or ['iou_nms', 'detection2mask', 'detection2mask_nopool', 'losses', 'prepare', 'prepare2', 'eval', 'detection', 's3dis', 'augment',
-                             's3dis_labels', 's3dis_full']
+                             's3dis_labels', 's3dis_full', 'sweep']
+    if 'sweep' in which:
+        gen_sweep()
     if 'iou_nms' in which:
         gen_iou_nms()
     if 'detection2mask' in which:

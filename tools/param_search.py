@@ -1,0 +1,99 @@
+"""Threshold search on the checkpoint tools/train_synthetic.py writes: every setting of the `*_th_search` grid (config.py; the
+reference's `--param_search`, models/evaluation.py:353-366) scored with the ScanNet AP over the validation scenes, in one pass.
+
+    python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 --checkpoint-dir /tmp/b2m_ckpt
+    python tools/param_search.py --checkpoint-dir /tmp/b2m_ckpt --scenes 4 --voxels 20000 [--batch-size 2] [--top 10] [--check 5]
+
+The scenes are train_synthetic's (seeds 0 .. scenes-1: it validates on the scenes it trains on).  Prints the best settings and the
+winner as an `eval_ths` line.  --check N re-evaluates N settings spread over the grid (the winner among them) through
+Model.pred2mask and eval_metric.compute_eval and compares the three averages exactly; a difference is an error.
+"""
+import argparse
+import os
+import sys
+import time
+import warnings
+from types import SimpleNamespace
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+from box2mask_amd import eval_metric, param_search, synth    # noqa: E402
+from box2mask_amd.config import scannet_config                # noqa: E402
+from box2mask_amd.model import Model                          # noqa: E402
+import train_synthetic as T                                   # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--checkpoint-dir', required=True)
+    ap.add_argument('--scenes', type=int, default=4)
+    ap.add_argument('--voxels', type=int, default=20000)
+    ap.add_argument('--batch-size', type=int, default=2)
+    ap.add_argument('--top', type=int, default=10, help='settings to print (0 = the whole table)')
+    ap.add_argument('--check', type=int, default=0, help='settings to re-evaluate through Model.pred2mask + compute_eval')
+    for axis in param_search.AXES:
+        ap.add_argument('--%s_search' % axis, nargs=3, type=float, default=None, metavar=('MIN', 'MAX', 'NUM'),
+                        help='np.linspace triple (default: config.py, the reference\'s)')
+    args = ap.parse_args(argv)
+    cfg = scannet_config(mlp_bb_scores_start_epoch=0)
+    cfg.checkpoint_path = args.checkpoint_dir.rstrip('/') + '/'
+    for axis in param_search.AXES:
+        if getattr(args, axis + '_search') is not None:
+            setattr(cfg, axis + '_search', getattr(args, axis + '_search'))
+    grid = param_search.ThresholdGrid.from_cfg(cfg)
+    model = Model(cfg, *synth.scannet_tables())
+    loaded = model.load_checkpoint()
+    if len(loaded) < 3:
+        raise SystemExit('no checkpoint under %s' % cfg.checkpoint_path)
+    model.eval()
+    sup = SimpleNamespace(smallest_bb_heuristic=True)
+    items, gts = [], {}
+    for b0 in range(0, args.scenes, args.batch_size):
+        batch, raws = T.build_batch(range(b0, min(b0 + args.batch_size, args.scenes)), args.voxels, 'train', sup)
+        pred = model.get_prediction(batch, with_grad=False, to_cpu=True, min_size=True)
+        items.append((batch, pred))
+        gts.update({r['name']: T.ground_truth_ids(r) for r in raws})
+    t0 = time.time()
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)
+        res = param_search.scannet_param_search(model, items, gts, grid)
+    dt = time.time() - t0
+    ap_ = res['ap']
+    settings = list(grid.settings())
+    key = lambda st: tuple(-np.inf if np.isnan(v) else v for v in (ap_[st][1], ap_[st][0]))
+    ranked = sorted(settings, key=lambda st: (tuple(-v for v in key(st)), st))
+    print('checkpoint %s: %d settings (%s) over %d scenes in %.1f s, %d distinct record sets matched'
+          % (loaded[2], len(settings), ' x '.join(str(n) for n in grid.shape), args.scenes, dt, res['n_evaluated']))
+    print('cluster_th score_th mask_bin_th mask_nms_th |     AP   AP50   AP25')
+    for st in ranked[:args.top or len(ranked)]:
+        print('%10.3f %8.3f %11.3f %11.3f | %6.3f %6.3f %6.3f' % (tuple(grid.eval_ths(*st)) + tuple(ap_[st])))
+    assert ranked[0] == res['best']
+    print('best: eval_ths = %s' % ' '.join('%.3f' % v for v in res['best_ths']))
+    if args.check:
+        picks = [settings[i] for i in np.unique(np.linspace(0, len(settings) - 1, args.check).round().astype(int))]
+        if res['best'] not in picks:
+            picks[-1] = res['best']
+        bad = 0
+        for st in picks:
+            model.cfg.eval_ths = grid.eval_ths(*st)
+            results = {}
+            for batch, pred in items:
+                results.update(model.pred2mask(batch, pred, 'eval'))
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore', RuntimeWarning)
+                avg, _ = eval_metric.compute_eval(results, gts)
+            want = [avg['all_ap'], avg['all_ap_50%'], avg['all_ap_25%']]
+            same = np.array_equal(ap_[st], want, equal_nan=True)
+            bad += not same
+            print('check %s: sweep %s  single-setting path %s  %s' % (grid.eval_ths(*st), ap_[st].tolist(), want, 'equal' if same else 'DIFFERENT'))
+        if bad:
+            raise SystemExit('%d of %d settings differ from the single-setting path' % (bad, len(picks)))
+    return res
+
+
+if __name__ == '__main__':
+    main()

@@ -104,10 +104,14 @@ def main(argv=None):
                     help='arkit: the oriented-box detection mAP (eval_detection.py) beside the ScanNet AP')
     ap.add_argument('--augment', action='store_true',
                     help='train on scenes augmented on the device, parameters drawn per scene per step (augment.py)')
+    ap.add_argument('--checkpoint-dir', default=None,
+                    help='keep the checkpoint here (tools/param_search.py reads it); default: a temporary directory')
     args = ap.parse_args(argv)
     torch.manual_seed(args.seed)
     cfg = scannet_config(lr=args.lr, mlp_bb_scores_start_epoch=0, half_training=bool(args.half))       # score head trained from the first step
-    cfg.checkpoint_path = tempfile.mkdtemp(prefix='b2m_ckpt_') + '/'
+    if args.checkpoint_dir:
+        os.makedirs(args.checkpoint_dir, exist_ok=True)
+    cfg.checkpoint_path = (args.checkpoint_dir.rstrip('/') if args.checkpoint_dir else tempfile.mkdtemp(prefix='b2m_ckpt_')) + '/'
     sup = SimpleNamespace(smallest_bb_heuristic=True)
     batch, raws = build_batch(range(args.scenes), args.voxels, 'train', sup)
     if args.augment:
