@@ -130,6 +130,10 @@ PROTOTYPES = {
     # ... nearest-neighbour index (box2mask_amd/neighbors.py)
     'b2m_nn_build': [P, I64, P, P],
     'b2m_nn_query': [P, I64, P, P, I64, P, P, P],
+    # ... ScanNet AP: matching and curves (box2mask_amd/eval_match.py)
+    'b2m_ap_rows': [P, I32, I32, P],
+    'b2m_ap_match': [P, I32, I64, P, P, P, I32, P, I64, P, P, P, I64, P, P, P, I32, P],
+    'b2m_ap_curve': [P, I64, P, P, I32, P, I64, I64, P, P, P, P],
 }
 PLAIN = {'b2m_last_error': (C.c_char_p, []), 'b2m_version': (C.c_int, []), 'b2m_device_ok': (C.c_int, []),
          'b2m_reload_env': (C.c_int, []),

@@ -444,11 +444,11 @@ class SelectionNet(ResNetBase):
                 }
         return results
 
-    def detection2mask_sweep(self, batch, pred, cfg, grid, gt_ids):
+    def detection2mask_sweep(self, batch, pred, cfg, grid, gt_ids, acc=None):
         """Every setting of a ``param_search.ThresholdGrid`` at once: one ``param_search.SweepTables`` per scene (host arrays), from
         which ``param_search.compose`` reads the surviving rows of any setting.  ScanNet flow only; see param_search.py."""
         from . import param_search
-        return param_search.sweep_tables(self, batch, pred, cfg, grid, gt_ids)
+        return param_search.sweep_tables(self, batch, pred, cfg, grid, gt_ids, acc=acc)
 
     # ------------------------------------------------------------------ prediction
     def get_prediction(self, batch, with_grad=True, to_cpu=False, to_numpy=False, min_size=True, sin=None):

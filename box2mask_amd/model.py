@@ -308,9 +308,10 @@ class Model:
     def pred2mask(self, batch, pred, mode):
         return self.detection_model.detection2mask(batch, pred, self.cfg, mode, True, *self.cfg.eval_ths)
 
-    def pred2mask_sweep(self, batch, pred, grid, gt_ids):
-        """The tables of a whole threshold grid (param_search.py) instead of the masks of cfg.eval_ths."""
-        return self.detection_model.detection2mask_sweep(batch, pred, self.cfg, grid, gt_ids)
+    def pred2mask_sweep(self, batch, pred, grid, gt_ids, acc=None):
+        """The tables of a whole threshold grid (param_search.py) instead of the masks of cfg.eval_ths.  With ``acc`` (an
+        ``eval_match.MatchAccumulator``) the stage results stay on the device and are matched there."""
+        return self.detection_model.detection2mask_sweep(batch, pred, self.cfg, grid, gt_ids, acc=acc)
 
     def parameters(self):
         return self.detection_model.parameters()

@@ -21,6 +21,8 @@ by default) and runs every setting as a CPU evaluation job of its own over the w
 So 600 settings cost 6 clusterings and 24 mask stages per batch, a few host reads per stage, and the host matching of
 ``eval_metric`` per setting.  ScanNet flow only (segment-level votes, mask NMS, the AP of eval_metric.py): that is what the
 reference's search scores.  ``compose`` and the matching are host logic like ``assign_from_counts``; every kernel stage is HIP.
+With ``matching='device'`` the matching, the curves and the AP run on the device as well (eval_match.py): the stage results are
+matched where they lie and nothing but an entry count per stage comes to the host.
 """
 from __future__ import annotations
 
@@ -158,9 +160,13 @@ def _cluster(sc, cluster_th, score_ths):
     return rs, out
 
 
-def sweep_tables(net, batch, pred, cfg, grid, gt_ids):
+def sweep_tables(net, batch, pred, cfg, grid, gt_ids, acc=None):
     """``SelectionNet.detection2mask_sweep``: one ``SweepTables`` per scene of the batch.  gt_ids: {scene name: (n_pts,) ids
-    ``label*1000 + instance``} or a list in scene order."""
+    ``label*1000 + instance``} or a list in scene order.
+
+    With ``acc`` (an ``eval_match.MatchAccumulator`` over all ``grid.settings()`` in grid order) the results of a stage are not
+    read to the host: its keep flags, labels and point histograms are matched where they lie, for the n_score x n_nms settings
+    of the stage in one launch, and the tables come back with ``clusters`` only (``stages`` stay empty lists)."""
     _lib.require_gpu()
     dev = torch.device('cuda', torch.cuda.current_device())
     sc = _scene_inputs(net, batch, pred, cfg, dev)
@@ -189,6 +195,9 @@ def sweep_tables(net, batch, pred, cfg, grid, gt_ids):
         for t, c in zip(tabs, cl):
             t.clusters.append(c)
             t.stages.append([])
+        ci = len(tabs[0].clusters) - 1
+        if acc is not None:                                                # the scores of the clusters, where the matching reads them
+            conf_dev = [d['boxes'][r.reps[:r.k].long(), 0].contiguous() for d, r in zip(sc, rs)]
         # rows no setting can keep are never projected: the prefix of the SMALLEST score_th (the grid is ascending)
         ksels = [int(c['ks'][0]) for c in cl]
         total = sum(ksels)
@@ -215,12 +224,15 @@ def sweep_tables(net, batch, pred, cfg, grid, gt_ids):
             row0 += k; boff += k * max(d['words'], 1); ioff += k * k; toff += d['n_vox'] * ((k + 63) // 64); hoff += k * d['G']
         tables_dev = torch.from_numpy(np.concatenate([desc.reshape(-1), hdesc.reshape(-1)])).to(dev)
         desc_ptr, hdesc_ptr = tables_dev.data_ptr(), tables_dev.data_ptr() + 8 * S * 20
-        for bth in grid.mask_bin_th:
+        for bi, bth in enumerate(grid.mask_bin_th):
             if total:
                 _call('b2m_mask_project_batch', desc_ptr, S, total, max_words, float(bth))
                 _call('b2m_mask_nms_sweep_batch', desc_ptr, S, max(ksels), ths_nms.ctypes.data, n_nms, res.data_ptr(), total)
                 _call('b2m_label_hist_batch', desc_ptr, S, total, n_class)
                 _call('b2m_mask_hist_index_batch', hdesc_ptr, S, max_words, max_pts)
+            if acc is not None:
+                _match_stage(acc, grid, ci, bi, tabs, sc, cl, ksels, conf_dev, res, n_nms, total, o_lab, o_hist)
+                continue
             host = res.cpu().numpy()                                       # the one host read of the stage
             row0 = hoff = 0
             for t, d, k in zip(tabs, sc, ksels):
@@ -229,6 +241,22 @@ def sweep_tables(net, batch, pred, cfg, grid, gt_ids):
                 t.stages[-1].append(dict(label_id=host[o_lab + row0:o_lab + row0 + k].copy(), inter=inter, keep=keep))
                 row0 += k; hoff += k * d['G']
     return tabs
+
+
+def _match_stage(acc, grid, ci, bi, tabs, sc, cl, ksels, conf_dev, res, n_nms, total, o_lab, o_hist):
+    """The (score_th, mask_nms_th) settings of stage (ci, bi) into ``acc``, straight from the stage's ``res`` buffer: setting
+    (si, mi) keeps row r of a scene iff r < ks[si] and flag row mi is set there."""
+    _, ns, nb, nm = grid.shape
+    pairs = [(si, mi) for si in range(ns) for mi in range(nm)]
+    set_id = [((ci * ns + si) * nb + bi) * nm + mi for si, mi in pairs]
+    prefix = [[int(c['ks'][si]) for si, _ in pairs] for c in cl]
+    scenes, row0, hoff = [], 0, 0
+    for t, d, k, cf in zip(tabs, sc, ksels, conf_dev):
+        scenes.append(dict(inter=res[o_hist + hoff:o_hist + hoff + k * d['G']].view(k, d['G']), label_id=res[o_lab + row0:o_lab + row0 + k],
+                           conf=cf, uniq=t.uniq, gt_vert=t.gt_vert, row0=row0))
+        row0 += k; hoff += k * d['G']
+    keep = res[:n_nms * total].view(n_nms, total) if total else None
+    acc.add(scenes, set_id, prefix, keep, [mi if total else -1 for _, mi in pairs])
 
 
 def materialize(net, batch, pred, cfg, grid, tables, ci, si, bi, mi):
@@ -258,16 +286,25 @@ def materialize(net, batch, pred, cfg, grid, tables, ci, si, bi, mi):
 
 
 # ----------------------------------------------------------------------------------------------------------------- the search
-def scannet_param_search(model, batches, gt_ids_by_scene, grid, per_class=False):
+def scannet_param_search(model, batches, gt_ids_by_scene, grid, per_class=False, matching='host'):
     """Score every setting of ``grid`` with the ScanNet AP over all ``batches``.
 
     batches: an iterable of batch dicts (predicted here with ``model.get_prediction``) or of ``(batch, pred)`` pairs.
     Returns dict(ap (nc, ns, nb, nm, 3) = AP, AP50, AP25 of every setting; best = its (ci, si, bi, mi) by AP50, then AP, then grid
     order; best_ths = that setting as ``eval_ths``; n_evaluated = the number of DISTINCT record sets matched; with per_class,
     ap_tables (nc, ns, nb, nm, 1, classes, overlaps) = what ``evaluate_matches`` returned).  The matching and the AP are the
-    unchanged host code of eval_metric, once per distinct record set."""
+    unchanged host code of eval_metric, once per distinct record set.
+
+    matching='device': the matching, the curves and the AP of EVERY setting on the device (box2mask_amd/eval_match.py) -- the
+    stage results are never read to the host, ``compose`` and ``records`` are not called, n_evaluated = the number of settings.
+    The AP of a curve of n points is then within 4 n 2^-53 of the host route's (the dot product is summed in ascending order
+    of the thresholds); ``best`` follows the same ranking over the device table."""
     shape = grid.shape
     settings = list(grid.settings())
+    if matching not in ('host', 'device'):
+        raise ValueError("matching must be 'host' or 'device', got %r" % (matching,))
+    if matching == 'device':
+        return _search_device(model, batches, gt_ids_by_scene, grid, per_class, shape, settings)
     matches = {st: {} for st in settings}
     keys = {st: [] for st in settings}
     for item in batches:
@@ -299,4 +336,26 @@ def scannet_param_search(model, batches, gt_ids_by_scene, grid, per_class=False)
     out = dict(ap=ap, best=best, best_ths=grid.eval_ths(*best), n_evaluated=len(done))
     if per_class:
         out['ap_tables'] = ap_tables
+    return out
+
+
+def _search_device(model, batches, gt_ids_by_scene, grid, per_class, shape, settings):
+    from . import eval_match
+    acc = eval_match.MatchAccumulator(len(settings))
+    for item in batches:
+        batch, pred = item if isinstance(item, (tuple, list)) else \
+            (item, model.get_prediction(item, with_grad=False, to_cpu=True, min_size=True))
+        model.pred2mask_sweep(batch, pred, grid, gt_ids_by_scene, acc=acc)
+    table = acc.finish()                                                   # (settings, classes, overlaps), grid order
+    ap = np.full(shape + (3,), np.nan)
+    for q, st in enumerate(settings):
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)
+            avg = eval_metric.compute_averages(table[q:q + 1])
+        ap[st] = (avg['all_ap'], avg['all_ap_50%'], avg['all_ap_25%'])
+    rank = lambda st: tuple(-np.inf if np.isnan(v) else v for v in (ap[st][1], ap[st][0]))
+    best = max(settings, key=lambda st: (rank(st), tuple(-i for i in st)))
+    out = dict(ap=ap, best=best, best_ths=grid.eval_ths(*best), n_evaluated=len(settings))
+    if per_class:
+        out['ap_tables'] = table.reshape(shape + (len(eval_metric.CLASS_LABELS), len(eval_metric.OVERLAPS)))[..., None, :, :].copy()
     return out

@@ -719,6 +719,62 @@ int b2m_paint_proposals(const uint64_t* bits, int64_t words, int32_t k, const in
 #define B2M_JOINT_HIST_MAX (1 << 24)
 int b2m_joint_hist(const int32_t* a, const int32_t* b, int64_t n, int32_t na, int32_t nb, int32_t* hist, void* stream);
 
+/* ---------------------------------------------------------------- ScanNet AP: matching and curves (box2mask_amd/eval_match.py)
+ * The second half of utils/eval_metric.py -- what assign_instances_for_scan (:281-345) derives from the intersection counts, the
+ * greedy matching of evaluate_matches (:102-199) for the ten overlaps and eighteen classes, the precision / recall curve and the
+ * AP (:205-247) -- for any number of SETTINGS at once (box2mask_amd/param_search.py scores 600).  The rule is the project's own
+ * eval_metric.assign_from_counts / evaluate_matches; tests/_ap_rule.py restates it over the flat arrays these entries take.
+ * Integers are reproduced exactly; precision, recall and the steps are the same fp64 operations; the AP is the dot product
+ * summed in ascending order of the thresholds (np.dot's order is the BLAS's).  Integer atomics only, and nothing that reaches a
+ * result depends on their order: the entries are sorted before they are read.
+ *
+ * `desc`: device array of n_scenes records of B2M_AP_DESC int64 fields (pointers stored as integers):
+ *    0 inter   int32[k][ld]: points shared by prediction row r and ground-truth id g (b2m_mask_hist / b2m_mask_hist_index)
+ *    1 k       prediction rows            2 g   ground-truth ids, <= B2M_AP_MAX_IDS            3 ld >= g
+ *    4 label   int32[k]: label_id of the rows                   5 conf  float[k]: their scores
+ *    6 gt      int32[3][g]: class index 0..17 of id / 1000 or -1 | 1 if id >= 1000 else 0 | points of the id (gt_vert)
+ *    7 rows    int32[3][k], written by b2m_ap_rows: vert = sum_g inter | void = sum over ids whose class index is -1 |
+ *              class index of the label when it is a valid class and vert >= 100, else -1 (the row does not count)
+ *    8 row0    first row of the scene in the launch's concatenated row list (keep flags, `taken`)
+ * The caller keeps every record within these limits (they are device memory; only the arguments are checked here). */
+#define B2M_AP_DESC 9
+#define B2M_AP_CLASSES 18
+#define B2M_AP_OVERLAPS 10
+#define B2M_AP_MAX_IDS 2048
+#define B2M_AP_MIN_REGION 100
+/* Field 7 of every scene from its fields 0-4 and 6: one thread per row.  max_k = the largest k of the table. */
+int b2m_ap_rows(const int64_t* desc, int32_t n_scenes, int32_t max_k, void* stream);
+/* The matching of every (scene, setting, class, overlap) of the table, one thread each.  Setting j < n_set of this launch is
+ * setting set_id[j] of all n_settings; in scene s it selects row r iff r < set_pref[s * n_set + j] (<= k of s) and
+ * (set_keep[j] < 0 or keep[set_keep[j] * keep_stride + row0 + r] != 0) -- the prefix and the flag row of the threshold sweep, read
+ * where b2m_mask_nms_sweep_batch left them; one setting with set_keep = -1 and set_pref = k is a plain evaluation.  Per item:
+ * the counted ground truths of the class (id >= 1000, gt_vert >= 100) in ascending g, the selected rows of the class in row
+ * order; a row taken by an earlier ground truth is skipped; the first row with (double)inter / max(gt_vert + vert - inter, 1) >
+ * ths_host[o] matches and is taken; a later one gives a false entry scored min(best, conf), raises best and is not taken; no
+ * match adds 1 to hard_fn, else one true entry scored best.  A row that exceeds the overlap with no ground truth of its class
+ * gives a false entry scored conf unless (void + inter with ids < 1000 + inter with ids under 100 points) / vert > ths_host[o].
+ * An entry is the uint64  (set_id * 180 + o * 18 + class) << 33 | order-preserving code of the float score << 1 | true, appended
+ * at entries[atomic (*n_entries)++] while that is below cap; *n_entries keeps counting past cap (the caller compares).  At most
+ * 12 entries per selected row: 3 at overlap 0.25, 1 at each of the nine overlaps >= 0.5.  hard_fn: int32[n_settings * 180],
+ * flags: int32[n_settings * 18] (bit 0: the class has a counted ground truth, bit 1: a counted selected row), both accumulated
+ * with integer atomics.  ths_host: the 10 fp64 overlaps, in HOST memory.  taken: n_set * 10 * total_k bytes of scratch, zeroed
+ * here (total_k = the sum of k). */
+int b2m_ap_match(const int64_t* desc, int32_t n_scenes, int64_t total_k, const int32_t* set_id, const int32_t* set_keep,
+                 const int32_t* set_pref, int32_t n_set, const int32_t* keep, int64_t keep_stride, const double* ths_host,
+                 void* taken, uint64_t* entries, int64_t cap, int64_t* n_entries, int32_t* hard_fn, int32_t* flags,
+                 int32_t n_settings, void* stream);
+/* ap[n_settings][18][10] fp64 from the n_keys entries of all scenes and batches SORTED ascending (b2m_sort_u64; padding behind
+ * n_keys is not read), one thread per (setting, overlap, class) segment: NaN without a counted ground truth, 0 with one and no
+ * counted row, else over the distinct scores in ascending order, j = 0 .. m - 1 with `below` = true entries under the score:
+ * tp = n_true - below, fp = entries at or above the score - tp, fn = below + hard_fn, precision = tp / (tp + fp), recall = tp /
+ * (tp + fn), the closing point (1, 0), steps[j] = 0.5 * r[j] - 0.5 * r[j + 2] over r = [recall[0], recall..., 0] and
+ * AP = sum_j precision[j] * steps[j] in ascending j, multiply and add separate.  Equal scores are one threshold.
+ * dbg_seg >= 0 names one segment (setting * 180 + overlap * 18 + class) whose curve is written as well: dbg_counts int64[3][dbg_cap]
+ * = tp | fp | fn per threshold, dbg_curve double[3][dbg_cap] = precision | recall | steps with the closing point, *dbg_n = m + 1
+ * (0 when the segment has no curve); points at or past dbg_cap are not written. */
+int b2m_ap_curve(const uint64_t* keys, int64_t n_keys, const int32_t* hard_fn, const int32_t* flags, int32_t n_settings,
+                 double* ap, int64_t dbg_seg, int64_t dbg_cap, int64_t* dbg_counts, double* dbg_curve, int64_t* dbg_n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,10 @@ box with 2.5 cm noise, score logits ~ N(0, 2)), the default 6 x 5 x 4
 Reports the device ms of the sweep's stages (HIP events round every launch, a pass of its own: the events serialise the stream),
 the wall time of the sweep up to the tables, the wall time of the host matching of all settings, and the looped path --
 Model.pred2mask + eval_metric.compute_eval per setting -- timed on `--loop-settings` settings spread evenly over the grid and
-scaled to the grid (0 = every setting).  The looped settings' APs are compared with the sweep's.  One JSON line at the end.
+scaled to the grid (0 = every setting).  The looped settings' APs are compared with the sweep's.  Then the same search with
+matching='device' (box2mask_amd/eval_match.py): its wall time up to the AP table beside the host route's of this very run, the
+device ms of its row-table, matching, sort and curve launches (HIP events round every launch, the median over `--device-runs`
+timed searches after a warm-up) and the largest difference between the two routes' averages.  One JSON line at the end.
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ from box2mask_amd import _lib, eval_metric, param_search, synth   # noqa: E402
 from box2mask_amd.config import scannet_config                    # noqa: E402
 from box2mask_amd.model import Model                              # noqa: E402
 
+AP_STAGES = ('b2m_ap_rows', 'b2m_ap_match', 'b2m_sort_u64', 'b2m_ap_curve')
 STAGES = ('b2m_nmc_batch', 'b2m_mask_project_batch', 'b2m_mask_nms_sweep_batch', 'b2m_label_hist_batch', 'b2m_mask_hist_index_batch')
 
 
@@ -43,6 +47,7 @@ def main(argv=None):
     ap.add_argument('--scenes', type=int, default=8)
     ap.add_argument('--voxels', type=int, default=150000)
     ap.add_argument('--loop-settings', type=int, default=12, help='settings the looped path is timed on, scaled to the grid (0 = all)')
+    ap.add_argument('--device-runs', type=int, default=5, help='timed searches with matching=device (median)')
     args = ap.parse_args(argv)
     cfg = scannet_config()
     model = Model(cfg, *synth.scannet_tables())
@@ -82,7 +87,38 @@ def main(argv=None):
     with warnings.catch_warnings():
         warnings.simplefilter('ignore', RuntimeWarning)
         res, search_s = wall(lambda: param_search.scannet_param_search(model, [(batch, pred)], gts, grid))
-    note('search %.1f s; the looped path ...' % search_s)
+    note('search %.1f s; the device route ...' % search_s)
+    # the same search with the matching on the device: wall time up to the AP table, then the device ms of its launches
+    device_search = lambda: param_search.scannet_param_search(model, [(batch, pred)], gts, grid, matching='device')
+    device_search()                                                                     # warm-up
+    walls, per_run = [], []
+    for _ in range(max(args.device_runs, 1)):
+        dres, dt = wall(device_search)
+        walls.append(dt)
+    for _ in range(max(args.device_runs, 1)):
+        rec_ap = []
+
+        def ap_hook(name, a, meta=None):
+            if name not in AP_STAGES:
+                return None
+            s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s_.record()
+
+            def done():
+                e_.record()
+                rec_ap.append((name, s_, e_))
+            return done
+        _lib.set_hook(ap_hook)
+        device_search()
+        torch.cuda.synchronize()
+        _lib.set_hook(None)
+        per_run.append({n: (sum(1 for m, _, _ in rec_ap if m == n), sum(s_.elapsed_time(e_) for m, s_, e_ in rec_ap if m == n))
+                        for n in AP_STAGES})
+    ap_stages = {n: {'launches': per_run[0][n][0], 'ms': round(float(np.median([r[n][1] for r in per_run])), 3)} for n in AP_STAGES}
+    both = ~np.isnan(res['ap'])
+    ap_diff = float(np.max(np.abs(dres['ap'] - res['ap'])[both], initial=0.0))
+    same_nan = bool(np.array_equal(np.isnan(dres['ap']), np.isnan(res['ap'])))
+    note('device search %.3f s; the looped path ...' % float(np.median(walls)))
     # the looped path on a subset
     settings = list(grid.settings())
     n_loop = n_set if args.loop_settings <= 0 else min(args.loop_settings, n_set)
@@ -110,6 +146,11 @@ def main(argv=None):
            'stages_device_ms': round(sum(v['ms'] for v in stages.values()), 3),
            'sweep_wall_s': round(sweep_s, 4), 'search_wall_s': round(search_s, 3),
            'host_matching_s': round(search_s - sweep_s, 3), 'distinct_record_sets_matched': res['n_evaluated'],
+           'device_search_wall_s': round(float(np.median(walls)), 4), 'device_search_wall_runs_s': [round(w, 4) for w in walls],
+           'device_stages': ap_stages,
+           'device_stages_device_ms': round(sum(v['ms'] for v in ap_stages.values()), 3),
+           'device_best_equals_host_best': dres['best'] == res['best'], 'device_vs_host_max_abs_diff': ap_diff,
+           'device_nan_pattern_equals_host': same_nan,
            'best': res['best_ths'], 'best_ap_ap50_ap25': [float(v) for v in res['ap'][res['best']]],
            'looped_settings_timed': len(chosen), 'looped_pred2mask_s': round(t_mask, 3), 'looped_compute_eval_s': round(t_eval, 3),
            'looped_scaled_to_grid_s': round((t_mask + t_eval) * scale, 1), 'looped_is_scaled': len(chosen) != n_set,

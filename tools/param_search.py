@@ -3,10 +3,13 @@ reference's `--param_search`, models/evaluation.py:353-366) scored with the Scan
 
     python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 --checkpoint-dir /tmp/b2m_ckpt
     python tools/param_search.py --checkpoint-dir /tmp/b2m_ckpt --scenes 4 --voxels 20000 [--batch-size 2] [--top 10] [--check 5]
+                                 [--matching host|device]
 
 The scenes are train_synthetic's (seeds 0 .. scenes-1: it validates on the scenes it trains on).  Prints the best settings and the
 winner as an `eval_ths` line.  --check N re-evaluates N settings spread over the grid (the winner among them) through
-Model.pred2mask and eval_metric.compute_eval and compares the three averages exactly; a difference is an error.
+Model.pred2mask and eval_metric.compute_eval and compares the three averages: exactly with --matching host; with --matching
+device (matching, curves and AP of every setting on the device, box2mask_amd/eval_match.py) within 4 n 2^-53 + 2^-50, n = one more
+than three entries per predicted mask of the setting (the longest curve it can give).  A difference is an error.
 """
 import argparse
 import os
@@ -35,6 +38,7 @@ def main(argv=None):
     ap.add_argument('--batch-size', type=int, default=2)
     ap.add_argument('--top', type=int, default=10, help='settings to print (0 = the whole table)')
     ap.add_argument('--check', type=int, default=0, help='settings to re-evaluate through Model.pred2mask + compute_eval')
+    ap.add_argument('--matching', choices=('host', 'device'), default='host', help='where the matching and the AP of the settings run')
     for axis in param_search.AXES:
         ap.add_argument('--%s_search' % axis, nargs=3, type=float, default=None, metavar=('MIN', 'MAX', 'NUM'),
                         help='np.linspace triple (default: config.py, the reference\'s)')
@@ -60,14 +64,15 @@ def main(argv=None):
     t0 = time.time()
     with warnings.catch_warnings():
         warnings.simplefilter('ignore', RuntimeWarning)
-        res = param_search.scannet_param_search(model, items, gts, grid)
+        res = param_search.scannet_param_search(model, items, gts, grid, matching=args.matching)
     dt = time.time() - t0
     ap_ = res['ap']
     settings = list(grid.settings())
     key = lambda st: tuple(-np.inf if np.isnan(v) else v for v in (ap_[st][1], ap_[st][0]))
     ranked = sorted(settings, key=lambda st: (tuple(-v for v in key(st)), st))
-    print('checkpoint %s: %d settings (%s) over %d scenes in %.1f s, %d distinct record sets matched'
-          % (loaded[2], len(settings), ' x '.join(str(n) for n in grid.shape), args.scenes, dt, res['n_evaluated']))
+    print('checkpoint %s: %d settings (%s) over %d scenes in %.1f s, %d %s'
+          % (loaded[2], len(settings), ' x '.join(str(n) for n in grid.shape), args.scenes, dt, res['n_evaluated'],
+             'distinct record sets matched' if args.matching == 'host' else 'settings matched on the device'))
     print('cluster_th score_th mask_bin_th mask_nms_th |     AP   AP50   AP25')
     for st in ranked[:args.top or len(ranked)]:
         print('%10.3f %8.3f %11.3f %11.3f | %6.3f %6.3f %6.3f' % (tuple(grid.eval_ths(*st)) + tuple(ap_[st])))
@@ -87,9 +92,14 @@ def main(argv=None):
                 warnings.simplefilter('ignore', RuntimeWarning)
                 avg, _ = eval_metric.compute_eval(results, gts)
             want = [avg['all_ap'], avg['all_ap_50%'], avg['all_ap_25%']]
-            same = np.array_equal(ap_[st], want, equal_nan=True)
+            if args.matching == 'host':
+                same = np.array_equal(ap_[st], want, equal_nan=True)
+            else:
+                bound = 4 * (3 * sum(int(r['mask'].shape[0]) for r in results.values()) + 1) * 2.0 ** -53 + 2.0 ** -50
+                same = np.array_equal(np.isnan(ap_[st]), np.isnan(want)) and \
+                    all(abs(a - b) <= bound for a, b in zip(ap_[st], want) if not np.isnan(b))
             bad += not same
-            print('check %s: sweep %s  single-setting path %s  %s' % (grid.eval_ths(*st), ap_[st].tolist(), want, 'equal' if same else 'DIFFERENT'))
+            print('check %s: sweep %s  single-setting path %s  %s' % (grid.eval_ths(*st), ap_[st].tolist(), want, ('equal' if args.matching == 'host' else 'within the bound') if same else 'DIFFERENT'))
         if bad:
             raise SystemExit('%d of %d settings differ from the single-setting path' % (bad, len(picks)))
     return res
