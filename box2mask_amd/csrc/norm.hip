@@ -3,67 +3,43 @@
 // Precision contract (tests/_norm_rule.py holds every path to it): the BatchNorm STATISTICS are fp64 sums of the fp32 inputs on
 // every path -- bn_stats_kernel, bn_small_fwd_kernel, the convolution's tile sums -- and the finalize math is fp64, one rounding per
 // fp32 constant.  The BACKWARD sums (sum g, sum g * xhat) go through the skeleton below: fp32 chains of at most 64 terms per
-// thread, fp64 from there on (the one-launch kernels: fp64 throughout).  The binary16 twins: the same, on the widened half inputs.
+// thread, fp64 from there on (the one-launch kernels: fp64 throughout).  The four row passes (statistics, apply, backward
+// reduction, backward apply) are ONE body each, `template <class T>` over the tensors' element type: T = float is the fp32
+// operator, T = _Float16 the half-precision one -- the same arithmetic on the widened inputs, one rounding to half on the way out.
 #include "b2m_common.h"
 
 #define RED_MAX_BLOCKS 1280   // 256 CUs x 5 resident blocks of bn_bwd_reduce: one full round, no tail (4096: 12 % slower)
 
-// Column reduction skeleton.  256 threads; thread -> (float4 column group cg, row slot rs).
-// F(row, cg) returns two float4 contributions (a, b); the block writes double partial sums
-// partial[blk*2c + col] (a) and partial[blk*2c + c + col] (b).
-template <class F>
-__device__ __forceinline__ void column_reduce(int64_t n, int c, double* __restrict__ partial, F f) {
-    extern __shared__ float red[];             // [nslots][c4][8]
-    const int c4 = c >> 2;
-    const int nslots = 256 / c4;
-    const int cg = threadIdx.x % c4, rs = threadIdx.x / c4;
-    const int64_t rows_per_blk = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_blk;
-    int64_t r1 = r0 + rows_per_blk;
-    if (r1 > n) r1 = n;
-    f32x4 sa = {0, 0, 0, 0}, sb = {0, 0, 0, 0};
-    if (rs < nslots) {
-        int64_t r = r0 + rs;
-        for (; r + 3 * nslots < r1; r += 4 * nslots) {  // four independent rows per iteration (memory-level parallelism)
-            f32x4 a0, b0, a1, b1, a2, b2, a3, b3;
-            f(r, cg, a0, b0);
-            f(r + nslots, cg, a1, b1);
-            f(r + 2 * nslots, cg, a2, b2);
-            f(r + 3 * nslots, cg, a3, b3);
-            sa += a0; sb += b0; sa += a1; sb += b1; sa += a2; sb += b2; sa += a3; sb += b3;
-        }
-        for (; r < r1; r += nslots) {
-            f32x4 a, b;
-            f(r, cg, a, b);
-            sa += a; sb += b;
-        }
-        float* p = red + ((size_t)rs * c4 + cg) * 8;
-        *(f32x4*)p = sa; *(f32x4*)(p + 4) = sb;
-    }
-    __syncthreads();
-    if (rs == 0) {
-        double da[4] = {0, 0, 0, 0}, db[4] = {0, 0, 0, 0};
-        for (int s = 0; s < nslots; ++s) {
-            const float* p = red + ((size_t)s * c4 + cg) * 8;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { da[u] += (double)p[u]; db[u] += (double)p[4 + u]; }
-        }
-        double* o = partial + (size_t)blockIdx.x * 2 * c;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { o[cg * 4 + u] = da[u]; o[c + cg * 4 + u] = db[u]; }
-    }
+// A 4-wide column group of a row, as fp32: the ONLY place where the element type of a tensor shows.  Binary16 (half-precision
+// training: the activations and their gradients live in HBM as IEEE half, every pass moves half the bytes): widened on load,
+// one rounding to half on store; 8-byte aligned rows where fp32 has 16-byte ones.
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *(const f32x4*)p; }
+__device__ __forceinline__ f32x4 ld4(const _Float16* p) {
+    const h16x4 v = *(const h16x4*)p;
+    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
 }
-// The same with the loads of four rows issued BEFORE any of them is used: `load(row, cg, in)` fills NIN float4 registers,
-// `f(in, a, b)` turns them into the two contributions.  In column_reduce the functor loads and computes, and with
-// wave-uniform branches inside it hipcc waited for every row's data before issuing the next row's loads: two or three
-// 16-byte loads in flight per thread, 3.5 TB/s; staged, eight to twelve.
+__device__ __forceinline__ void st4(float* p, const f32x4 v) { *(f32x4*)p = v; }
+__device__ __forceinline__ void st4(_Float16* p, const f32x4 v) {
+    h16x4 h;
+    h[0] = (_Float16)v[0]; h[1] = (_Float16)v[1]; h[2] = (_Float16)v[2]; h[3] = (_Float16)v[3];
+    *(h16x4*)p = h;
+}
+
+// Column reduction skeleton.  256 threads; thread -> (float4 column group cg, row slot rs); a block owns a contiguous row range.
+// `load(row, cg, in)` fills NIN float4 registers, `f(in, a, b)` (NS == 3: `f(in, a, b, c)`) turns them into the NS float4
+// contributions; the block writes double partial sums partial[blk * NS * c + k * c + col] for sum k.  The loads of four rows are
+// issued BEFORE any of them is used: with wave-uniform branches inside a functor that loads and computes, hipcc waited for every
+// row's data before issuing the next row's loads -- two or three 16-byte loads in flight per thread, 3.5 TB/s; staged, eight to twelve.
 // ACC: the type a thread accumulates in and the block's LDS slots hold -- float (fp32 chains of at most 64 terms for c <= 256,
 // n <= 327 680; fp64 from the block combine on) or double (`f` then fills double4 contributions: the BatchNorm statistics).
-template <int NIN, class ACC = float, class L, class F>
+// The two or three sums are written out (sa, sb, sc), one reference per sum for the functor: as arrays of NS walked by loops the
+// same arithmetic compiles to another instruction order in EVERY kernel built on this (profiles/bn_refactor.md, section 2).
+template <int NIN, class ACC = float, int NS = 2, class L, class F>
 __device__ __forceinline__ void column_reduce_staged(int64_t n, int c, double* __restrict__ partial, L load, F f) {
     typedef ACC acc4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) unsigned char red_raw[];
-    ACC* red = (ACC*)red_raw;                  // [nslots][c4][8]
+    ACC* red = (ACC*)red_raw;                  // [nslots][c4][4 * NS]
     const int c4 = c >> 2;
     const int nslots = 256 / c4;
     const int cg = threadIdx.x % c4, rs = threadIdx.x / c4;
@@ -71,7 +47,8 @@ __device__ __forceinline__ void column_reduce_staged(int64_t n, int c, double* _
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_blk;
     int64_t r1 = r0 + rows_per_blk;
     if (r1 > n) r1 = n;
-    acc4 sa = {0, 0, 0, 0}, sb = {0, 0, 0, 0};
+    static_assert(NS == 2 || NS == 3, "two or three sums");
+    acc4 sa = {0, 0, 0, 0}, sb = {0, 0, 0, 0}, sc = {0, 0, 0, 0};      // (sc: NS == 3 only)
     if (rs < nslots) {
         int64_t r = r0 + rs;
         for (; r + 3 * nslots < r1; r += 4 * nslots) {
@@ -81,32 +58,41 @@ __device__ __forceinline__ void column_reduce_staged(int64_t n, int c, double* _
             __builtin_amdgcn_sched_barrier(0);         // (left alone, the scheduler sinks each load to its first use)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                acc4 a, b;
-                f(in[u], a, b);
+                acc4 a, b, cc;
+                if constexpr (NS == 3) f(in[u], a, b, cc); else f(in[u], a, b);
                 sa += a; sb += b;
+                if constexpr (NS == 3) sc += cc;
             }
         }
         for (; r < r1; r += nslots) {
             f32x4 in[NIN];
-            acc4 a, b;
+            acc4 a, b, cc;
             load(r, cg, in);
-            f(in, a, b);
+            if constexpr (NS == 3) f(in, a, b, cc); else f(in, a, b);
             sa += a; sb += b;
+            if constexpr (NS == 3) sc += cc;
         }
-        ACC* p = red + ((size_t)rs * c4 + cg) * 8;
+        ACC* p = red + ((size_t)rs * c4 + cg) * (4 * NS);
         *(acc4*)p = sa; *(acc4*)(p + 4) = sb;
+        if constexpr (NS == 3) *(acc4*)(p + 8) = sc;
     }
     __syncthreads();
     if (rs == 0) {
-        double da[4] = {0, 0, 0, 0}, db[4] = {0, 0, 0, 0};
+        double da[4] = {0, 0, 0, 0}, db[4] = {0, 0, 0, 0}, dc[4] = {0, 0, 0, 0};
         for (int s = 0; s < nslots; ++s) {
-            const ACC* p = red + ((size_t)s * c4 + cg) * 8;
+            const ACC* p = red + ((size_t)s * c4 + cg) * (4 * NS);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { da[u] += (double)p[u]; db[u] += (double)p[4 + u]; }
+            for (int u = 0; u < 4; ++u) {
+                da[u] += (double)p[u]; db[u] += (double)p[4 + u];
+                if constexpr (NS == 3) dc[u] += (double)p[8 + u];
+            }
         }
-        double* o = partial + (size_t)blockIdx.x * 2 * c;
+        double* o = partial + (size_t)blockIdx.x * NS * c;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) { o[cg * 4 + u] = da[u]; o[c + cg * 4 + u] = db[u]; }
+        for (int u = 0; u < 4; ++u) {
+            o[cg * 4 + u] = da[u]; o[c + cg * 4 + u] = db[u];
+            if constexpr (NS == 3) o[2 * c + cg * 4 + u] = dc[u];
+        }
     }
 }
 // one wave per output column: lanes sum strided partials, then a fixed-order shuffle tree (deterministic)
@@ -132,30 +118,52 @@ static int reduce_blocks(int64_t n) {
     if (b > RED_MAX_BLOCKS) b = RED_MAX_BLOCKS;
     return (int)b;
 }
+// LDS of a skeleton launch: [nslots][c4][4 * ns] accumulators of acc_bytes each
+static size_t reduce_lds(int c, int ns, size_t acc_bytes) {
+    const int c4 = c / 4, nslots = 256 / c4;
+    return (size_t)nslots * c4 * 4 * ns * acc_bytes;
+}
 
 // ------------------------------------------------------------------ BN forward
-// Statistics from x (here and in bn_stats_h_kernel, the binary16 twin): the skeleton with FP64 accumulators -- every element is
-// widened before it is added, and x * x is exact in a double -- as bn_small_fwd_kernel and the convolution's tile sums do.  The variance is the difference of the two sums: with fp32
+// Statistics from x: the skeleton with FP64 accumulators -- every element is widened before it is added, and x * x is exact in a
+// double -- as bn_small_fwd_kernel and the convolution's tile sums do.  The variance is the difference of the two sums: with fp32
 // chains a column whose |mean| is 100 sigma loses about 160 ulps of invstd and one at 1000 sigma 7e-4 relative (SIMULATED in numpy
 // with this launch geometry, not measured on a device; tests/test_norm_rule.py repeats the simulation with chains of 25 rows).  With
 // fp64 sums every path rounds to the fp32 constants of the exact value.  Three fp64 operations per element loaded: HBM-bound.
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int c,
+template <class T>
+__global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, int64_t ldx, int64_t n, int c,
                                                        double* __restrict__ partial) {
     typedef double f64x4 __attribute__((ext_vector_type(4)));
     column_reduce_staged<1, double>(n, c, partial,
-        [&](int64_t r, int cg, f32x4 (&in)[1]) { in[0] = *(const f32x4*)(x + r * ldx + cg * 4); },
+        [&](int64_t r, int cg, f32x4 (&in)[1]) { in[0] = ld4(x + r * ldx + cg * 4); },
         [&](const f32x4 (&in)[1], f64x4& a, f64x4& b) { a = __builtin_convertvector(in[0], f64x4); b = a * a; });
+}
+// the statistics pass over x: partial[nblk][2c]; returns nblk for the launch that finishes the sums
+template <class T>
+static int launch_bn_stats(const T* x, int64_t ldx, int64_t n, int c, double* partial, hipStream_t st) {
+    const int nblk = reduce_blocks(n);
+    bn_stats_kernel<T><<<nblk, 256, reduce_lds(c, 2, sizeof(double)), st>>>(x, ldx, n, c, partial);
+    return nblk;
+}
+template <class T>
+static void launch_bn_stats_sums(const T* x, int64_t ldx, int64_t n, int c, double* partial, double* stats, hipStream_t st) {
+    const int nblk = launch_bn_stats(x, ldx, n, c, partial, st);
+    reduce_final_kernel<<<2 * c, 64, 0, st>>>(partial, nblk, 2 * c, stats, nullptr, nullptr);
 }
 extern "C" int b2m_bn_stats(const float* x, int64_t ldx, int64_t n, int32_t c, double* partial, double* stats,
                             void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     B2M_CHECK_ARG(x && partial && stats && c > 0 && c % 4 == 0 && c <= 1024 && ldx % 4 == 0 && ldx >= c,
                   "c and ldx must be multiples of 4, c <= 1024");
     B2M_CHECK_ARG(((uintptr_t)x % 16) == 0, "x must be 16-byte aligned");
-    const int nblk = reduce_blocks(n);
-    const int c4 = c / 4, nslots = 256 / c4;
-    bn_stats_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(double), st>>>(x, ldx, n, c, partial);
-    reduce_final_kernel<<<2 * c, 64, 0, st>>>(partial, nblk, 2 * c, stats, nullptr, nullptr);
+    launch_bn_stats_sums(x, ldx, n, c, partial, stats, (hipStream_t)stream);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+extern "C" int b2m_bn_stats_h(const void* x, int64_t ldx, int64_t n, int32_t c, double* partial, double* stats, void* stream) {
+    B2M_CHECK_ARG(x && partial && stats && c > 0 && c % 4 == 0 && c <= 1024 && ldx % 4 == 0 && ldx >= c && n >= 1,
+                  "c and ldx must be multiples of 4, c <= 1024");
+    B2M_CHECK_ARG(((uintptr_t)x % 8) == 0, "x must be 8-byte aligned");
+    launch_bn_stats_sums((const _Float16*)x, ldx, n, c, partial, stats, (hipStream_t)stream);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }
@@ -223,19 +231,35 @@ __global__ __launch_bounds__(64) void bn_final_finalize_kernel(const double* __r
     scale[j] = (float)(g * is);
     shift[j] = (float)(b - m * g * is);
 }
+// statistics + finalize of a tensor in two launches
+template <class T>
+static void launch_bn_stats_finalize(const T* x, int64_t ldx, int64_t n, int c, double* partial, double* stats, const float* gamma,
+                                     const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                                     float* mean, float* invstd, float* scale, float* shift, hipStream_t st) {
+    const int nblk = launch_bn_stats(x, ldx, n, c, partial, st);
+    bn_final_finalize_kernel<<<c, 64, 0, st>>>(partial, nblk, (double)n, c, gamma, beta, eps, momentum, running_mean,
+                                               running_var, mean, invstd, scale, shift, stats);
+}
 extern "C" int b2m_bn_stats_finalize(const float* x, int64_t ldx, int64_t n, int32_t c, double* partial, double* stats,
                                      const float* gamma, const float* beta, float eps, float momentum,
                                      float* running_mean, float* running_var, float* mean, float* invstd, float* scale,
                                      float* shift, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     B2M_CHECK_ARG(x && partial && scale && shift && c > 0 && c % 4 == 0 && c <= 1024 && ldx % 4 == 0 && ldx >= c,
                   "c and ldx must be multiples of 4, c <= 1024");
     B2M_CHECK_ARG(((uintptr_t)x % 16) == 0 && n >= 1, "x must be 16-byte aligned, n >= 1");
-    const int nblk = reduce_blocks(n);
-    const int c4 = c / 4, nslots = 256 / c4;
-    bn_stats_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(double), st>>>(x, ldx, n, c, partial);
-    bn_final_finalize_kernel<<<c, 64, 0, st>>>(partial, nblk, (double)n, c, gamma, beta, eps, momentum, running_mean,
-                                               running_var, mean, invstd, scale, shift, stats);
+    launch_bn_stats_finalize(x, ldx, n, c, partial, stats, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
+                             scale, shift, (hipStream_t)stream);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+extern "C" int b2m_bn_stats_finalize_h(const void* x, int64_t ldx, int64_t n, int32_t c, double* partial, const float* gamma,
+                                       const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                                       float* mean, float* invstd, float* scale, float* shift, void* stream) {
+    B2M_CHECK_ARG(x && partial && scale && shift && c > 0 && c % 4 == 0 && c <= 1024 && ldx % 4 == 0 && ldx >= c && n >= 1,
+                  "c and ldx must be multiples of 4, c <= 1024");
+    B2M_CHECK_ARG(((uintptr_t)x % 8) == 0, "x must be 8-byte aligned");
+    launch_bn_stats_finalize((const _Float16*)x, ldx, n, c, partial, nullptr, gamma, beta, eps, momentum, running_mean,
+                             running_var, mean, invstd, scale, shift, (hipStream_t)stream);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }
@@ -355,25 +379,26 @@ extern "C" int b2m_bn_finalize(const double* stats, double count, const double* 
     return B2M_OK;
 }
 
-__global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int c4,
+template <class T>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, int64_t ldx, int64_t n, int c4,
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
-                                                       const float* __restrict__ res, int64_t ldr, int relu,
-                                                       float* __restrict__ y, int64_t ldy) {
+                                                       const T* __restrict__ res, int64_t ldr, int relu,
+                                                       T* __restrict__ y, int64_t ldy) {
     // thread -> (row slot, float4 column group); rows are walked with a constant stride: no per-element division
     const int nslots = 256 / c4;
     const int cg = threadIdx.x % c4, rs = threadIdx.x / c4;
     if (rs >= nslots) return;
     const f32x4 s = *(const f32x4*)(scale + cg * 4), b = *(const f32x4*)(shift + cg * 4);
     for (int64_t r = (int64_t)blockIdx.x * nslots + rs; r < n; r += (int64_t)gridDim.x * nslots) {
-        f32x4 v = *(const f32x4*)(x + r * ldx + cg * 4);
+        f32x4 v = ld4(x + r * ldx + cg * 4);
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = __builtin_fmaf(v[u], s[u], b[u]);    // the backward recomputes this sign
-        if (res) v += *(const f32x4*)(res + r * ldr + cg * 4);
+        if (res) v += ld4(res + r * ldr + cg * 4);
         if (relu) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) v[u] = v[u] > 0.f ? v[u] : 0.f;
         }
-        *(f32x4*)(y + r * ldy + cg * 4) = v;
+        st4(y + r * ldy + cg * 4, v);
     }
 }
 // grid for the row-chunk elementwise kernels: blocks of (256/c4) rows, enough blocks to fill the chip
@@ -406,6 +431,11 @@ __global__ __launch_bounds__(256) void bn_apply_elem_kernel(const float* x, int6
         y[r * ldy + col] = v;
     }
 }
+template <class T>
+static void launch_bn_apply(const T* x, int64_t ldx, int64_t n, int c, const float* scale, const float* shift, const T* residual,
+                            int64_t ldr, int relu, T* y, int64_t ldy, hipStream_t st) {
+    bn_apply_kernel<T><<<row_grid(n, c / 4), 256, 0, st>>>(x, ldx, n, c / 4, scale, shift, residual, ldr, relu, y, ldy);
+}
 extern "C" int b2m_bn_apply(const float* x, int64_t ldx, int64_t n, int32_t c, const float* scale, const float* shift,
                             const float* residual, int64_t ldr, int32_t relu, float* y, int64_t ldy, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -419,16 +449,31 @@ extern "C" int b2m_bn_apply(const float* x, int64_t ldx, int64_t n, int32_t c, c
     }
     if (n == 0) return B2M_OK;
     B2M_CHECK_ARG(c <= 1024, "c <= 1024");
-    bn_apply_kernel<<<row_grid(n, c / 4), 256, 0, st>>>(x, ldx, n, c / 4, scale, shift, residual, ldr, relu, y, ldy);
+    launch_bn_apply(x, ldx, n, c, scale, shift, residual, ldr, relu, y, ldy, st);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+extern "C" int b2m_bn_apply_h(const void* x, int64_t ldx, int64_t n, int32_t c, const float* scale, const float* shift,
+                              const void* residual, int64_t ldr, int32_t relu, void* y, int64_t ldy, void* stream) {
+    B2M_CHECK_ARG(x && y && scale && shift && c > 0 && c % 4 == 0 && c <= 1024 && ldx % 4 == 0 && ldy % 4 == 0 &&
+                      (!residual || ldr % 4 == 0), "c and leading dimensions must be multiples of 4, c <= 1024");
+    B2M_CHECK_ARG(((uintptr_t)x % 8) == 0 && ((uintptr_t)y % 8) == 0 && ((uintptr_t)residual % 8) == 0, "8-byte aligned rows");
+    if (n == 0) return B2M_OK;
+    launch_bn_apply((const _Float16*)x, ldx, n, c, scale, shift, (const _Float16*)residual, ldr, relu, (_Float16*)y, ldy,
+                    (hipStream_t)stream);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }
 
 // ------------------------------------------------------------------ BN backward
-template <bool RELU, bool HASY>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, int64_t lddy,
-                                                            const float* __restrict__ y, int64_t ldy,
-                                                            const float* __restrict__ x, int64_t ldx, int64_t n, int c,
+// The ReLU mask: where a residual is fused (HASY), the stored output's sign -- for T = _Float16 that is y > 0 on the half value
+// the next layer saw; where none is, the sign of the forward's fp32 fmaf(x, scale, shift), recomputed from the x the kernel reads
+// anyway: one tensor read less, and the forward need not keep y.  (In binary16 y is no faithful witness there: a positive value
+// below 2^-25 stores as 0 and still counts as on -- the derivative of the unrounded function; tests/_norm_rule.py, bn_check_half.)
+template <class T, bool RELU, bool HASY>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dy, int64_t lddy,
+                                                            const T* __restrict__ y, int64_t ldy,
+                                                            const T* __restrict__ x, int64_t ldx, int64_t n, int c,
                                                             const float* __restrict__ mean,
                                                             const float* __restrict__ invstd,
                                                             const float* __restrict__ mscale,
@@ -442,9 +487,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
     constexpr int NIN = HASY ? 3 : 2;
     column_reduce_staged<NIN>(n, c, partial,
         [&](int64_t r, int cg, f32x4 (&in)[NIN]) {
-            in[0] = *(const f32x4*)(dy + r * lddy + cg * 4);
-            in[1] = *(const f32x4*)(x + r * ldx + cg * 4);
-            if constexpr (HASY) in[2] = *(const f32x4*)(y + r * ldy + cg * 4);
+            in[0] = ld4(dy + r * lddy + cg * 4);
+            in[1] = ld4(x + r * ldx + cg * 4);
+            if constexpr (HASY) in[2] = ld4(y + r * ldy + cg * 4);
         },
         [&](const f32x4 (&in)[NIN], f32x4& a, f32x4& b) {
             f32x4 g = in[0];
@@ -462,29 +507,52 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
             a = g; b = g * ((xx - m) * is);
         });
 }
+// param_grad_scale: the factor of the fp32 copies dbeta / dgamma (half-precision training un-scales the loss scale there)
+template <class T>
+static void launch_bn_bwd_reduce(const T* dy, int64_t lddy, const T* y, int64_t ldy, const T* x, int64_t ldx, int64_t n, int c,
+                                 const float* mean, const float* invstd, int relu, const float* mask_scale,
+                                 const float* mask_shift, double* partial, double* sums, float* dbeta_f32, float* dgamma_f32,
+                                 float param_grad_scale, hipStream_t st) {
+    const int nblk = reduce_blocks(n);
+    const size_t lds = reduce_lds(c, 2, sizeof(float));
+    if (!relu) bn_bwd_reduce_kernel<T, false, false><<<nblk, 256, lds, st>>>(dy, lddy, nullptr, 0, x, ldx, n, c, mean, invstd, nullptr, nullptr, partial);
+    else if (y) bn_bwd_reduce_kernel<T, true, true><<<nblk, 256, lds, st>>>(dy, lddy, y, ldy, x, ldx, n, c, mean, invstd, nullptr, nullptr, partial);
+    else bn_bwd_reduce_kernel<T, true, false><<<nblk, 256, lds, st>>>(dy, lddy, nullptr, 0, x, ldx, n, c, mean, invstd, mask_scale, mask_shift, partial);
+    reduce_final_kernel<<<2 * c, 64, 0, st>>>(partial, nblk, 2 * c, sums, dbeta_f32, dgamma_f32, param_grad_scale);
+}
 extern "C" int b2m_bn_bwd_reduce(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* x,
                                  int64_t ldx, int64_t n, int32_t c, const float* mean, const float* invstd,
                                  int32_t relu, const float* mask_scale, const float* mask_shift, double* partial,
                                  double* sums, float* dbeta_f32, float* dgamma_f32, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     B2M_CHECK_ARG(dy && x && mean && invstd && partial && sums && (!relu || y || (mask_scale && mask_shift)),
                   "NULL argument (relu needs y, or mask_scale and mask_shift)");
     B2M_CHECK_ARG(c > 0 && c % 4 == 0 && c <= 1024 && lddy % 4 == 0 && ldx % 4 == 0 && (!relu || ldy % 4 == 0),
                   "c and leading dimensions must be multiples of 4");
-    const int nblk = reduce_blocks(n);
-    const int c4 = c / 4, nslots = 256 / c4;
-    const size_t lds = (size_t)nslots * c4 * 8 * sizeof(float);
-    if (!relu) bn_bwd_reduce_kernel<false, false><<<nblk, 256, lds, st>>>(dy, lddy, nullptr, 0, x, ldx, n, c, mean, invstd, nullptr, nullptr, partial);
-    else if (y) bn_bwd_reduce_kernel<true, true><<<nblk, 256, lds, st>>>(dy, lddy, y, ldy, x, ldx, n, c, mean, invstd, nullptr, nullptr, partial);
-    else bn_bwd_reduce_kernel<true, false><<<nblk, 256, lds, st>>>(dy, lddy, nullptr, 0, x, ldx, n, c, mean, invstd, mask_scale, mask_shift, partial);
-    reduce_final_kernel<<<2 * c, 64, 0, st>>>(partial, nblk, 2 * c, sums, dbeta_f32, dgamma_f32);
+    launch_bn_bwd_reduce(dy, lddy, y, ldy, x, ldx, n, c, mean, invstd, relu, mask_scale, mask_shift, partial, sums, dbeta_f32,
+                         dgamma_f32, 1.f, (hipStream_t)stream);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+extern "C" int b2m_bn_bwd_reduce_h(const void* dy, int64_t lddy, const void* y, int64_t ldy, const void* x, int64_t ldx,
+                                   int64_t n, int32_t c, const float* mean, const float* invstd, int32_t relu,
+                                   const float* mask_scale, const float* mask_shift, double* partial,
+                                   double* sums, float* dbeta_f32, float* dgamma_f32, float param_grad_scale, void* stream) {
+    B2M_CHECK_ARG(dy && x && mean && invstd && partial && sums && (!relu || y || (mask_scale && mask_shift)),
+                  "NULL argument (relu needs y, or mask_scale and mask_shift)");
+    B2M_CHECK_ARG(c > 0 && c % 4 == 0 && c <= 1024 && lddy % 4 == 0 && ldx % 4 == 0 && (!relu || !y || ldy % 4 == 0) && n >= 1,
+                  "c and leading dimensions must be multiples of 4");
+    B2M_CHECK_ARG(((uintptr_t)dy % 8) == 0 && ((uintptr_t)x % 8) == 0 && ((uintptr_t)y % 8) == 0, "8-byte aligned rows");
+    launch_bn_bwd_reduce((const _Float16*)dy, lddy, (const _Float16*)y, ldy, (const _Float16*)x, ldx, n, c, mean, invstd, relu,
+                         mask_scale, mask_shift, partial, sums, dbeta_f32, dgamma_f32, param_grad_scale, (hipStream_t)stream);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, int64_t lddy,
-                                                           const float* __restrict__ y, int64_t ldy,
-                                                           const float* __restrict__ x, int64_t ldx, int64_t n, int c,
+// mscale / mshift: NULL unless the mask is recomputed from x (the launch passes them only where y is absent)
+template <class T>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dy, int64_t lddy,
+                                                           const T* __restrict__ y, int64_t ldy,
+                                                           const T* __restrict__ x, int64_t ldx, int64_t n, int c,
                                                            const float* __restrict__ mean,
                                                            const float* __restrict__ invstd,
                                                            const float* __restrict__ gamma,
@@ -492,8 +560,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const double* __restrict__ count_dev, int relu,
                                                            const float* __restrict__ mscale,
                                                            const float* __restrict__ mshift,
-                                                           float* __restrict__ dx, int64_t lddx,
-                                                           float* __restrict__ dres, int64_t lddres) {
+                                                           T* __restrict__ dx, int64_t lddx,
+                                                           T* __restrict__ dres, int64_t lddres) {
     const int c4 = c >> 2;
     const float inv_n = (float)(1.0 / (count_dev ? *count_dev : count_host));
     const int nslots = 256 / c4;
@@ -509,11 +577,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         ga[u] = (gamma ? gamma[cg * 4 + u] : 1.f) * is[u];
     }
     for (int64_t r = (int64_t)blockIdx.x * nslots + rs; r < n; r += (int64_t)gridDim.x * nslots) {
-        f32x4 g = *(const f32x4*)(dy + r * lddy + cg * 4);
-        const f32x4 xx = *(const f32x4*)(x + r * ldx + cg * 4);
+        f32x4 g = ld4(dy + r * lddy + cg * 4);
+        const f32x4 xx = ld4(x + r * ldx + cg * 4);
         if (relu) {
             f32x4 yy;
-            if (y) yy = *(const f32x4*)(y + r * ldy + cg * 4);
+            if (y) yy = ld4(y + r * ldy + cg * 4);
             else {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) yy[u] = __builtin_fmaf(xx[u], msc[u], msh[u]);
@@ -527,16 +595,25 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             const float xh = (xx[u] - m[u]) * is[u];
             out[u] = ga[u] * (g[u] - sg[u] - xh * sgx[u]);
         }
-        *(f32x4*)(dx + r * lddx + cg * 4) = out;
-        if (dres) *(f32x4*)(dres + r * lddres + cg * 4) = g;
+        st4(dx + r * lddx + cg * 4, out);
+        if (dres) st4(dres + r * lddres + cg * 4, g);
     }
+}
+template <class T>
+static void launch_bn_bwd_apply(const T* dy, int64_t lddy, const T* y, int64_t ldy, const T* x, int64_t ldx, int64_t n, int c,
+                                const float* mean, const float* invstd, const float* gamma, const double* sums, double count,
+                                const double* count_dev, int relu, const float* mask_scale, const float* mask_shift, T* dx,
+                                int64_t lddx, T* dres, int64_t lddres, hipStream_t st) {
+    const bool from_x = relu && !y;         // (the entries have checked that both constants are there then)
+    bn_bwd_apply_kernel<T><<<row_grid(n, c / 4), 256, 0, st>>>(dy, lddy, y, ldy, x, ldx, n, c, mean, invstd, gamma, sums, count,
+                                                                count_dev, relu, from_x ? mask_scale : nullptr,
+                                                                from_x ? mask_shift : nullptr, dx, lddx, dres, lddres);
 }
 extern "C" int b2m_bn_bwd_apply(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* x,
                                 int64_t ldx, int64_t n, int32_t c, const float* mean, const float* invstd,
                                 const float* gamma, const double* sums, double count, const double* count_dev,
                                 int32_t relu, const float* mask_scale, const float* mask_shift, float* dx, int64_t lddx, float* dres,
                                 int64_t lddres, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     B2M_CHECK_ARG(dy && x && mean && invstd && sums && dx && (!relu || y || (mask_scale && mask_shift)),
                   "NULL argument (relu needs y, or mask_scale and mask_shift)");
     B2M_CHECK_ARG(c > 0 && c % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && (!relu || ldy % 4 == 0) &&
@@ -544,205 +621,15 @@ extern "C" int b2m_bn_bwd_apply(const float* dy, int64_t lddy, const float* y, i
                   "c and leading dimensions must be multiples of 4");
     if (n == 0) return B2M_OK;
     B2M_CHECK_ARG(c <= 1024, "c <= 1024");
-    bn_bwd_apply_kernel<<<row_grid(n, c / 4), 256, 0, st>>>(dy, lddy, y, ldy, x, ldx, n, c, mean, invstd, gamma, sums,
-                                                             count, count_dev, relu, y ? nullptr : mask_scale,
-                                                             y ? nullptr : mask_shift, dx, lddx, dres, lddres);
+    launch_bn_bwd_apply(dy, lddy, y, ldy, x, ldx, n, c, mean, invstd, gamma, sums, count, count_dev, relu, mask_scale, mask_shift,
+                        dx, lddx, dres, lddres, (hipStream_t)stream);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
-}
-
-// ------------------------------------------------------------------ half-precision training: BatchNorm with binary16 I/O
-// (round 6; /root/reference/configs/arkitscenes.txt is the workload BASELINE names for it.)  The activations and their gradients live
-// in HBM as IEEE half -- every pass below moves half the bytes of its fp32 twin --; statistics, the per-column constants and
-// all arithmetic stay fp32 / fp64 exactly as above (the statistics: fp64 accumulators, as bn_stats_kernel), one rounding to half
-// on the way out.  The ReLU mask: where a residual is fused, the stored output's sign (y > 0 on the half value the next layer saw);
-// where none is, the sign of the forward's fp32 fmaf(x, scale, shift), recomputed from x (see bn_bwd_reduce_h_kernel: y is not a
-// faithful witness there -- a positive value below 2^-25 stores as 0 and still counts as on).  tests/_norm_rule.py (bn_check_half)
-// holds both.  Pitches in ELEMENTS, multiples of 4; 8-byte aligned rows.
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 ldh4(const _Float16* p) {
-    const h16x4 v = *(const h16x4*)p;
-    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-__device__ __forceinline__ void sth4(_Float16* p, const f32x4 v) {
-    h16x4 h;
-    h[0] = (_Float16)v[0]; h[1] = (_Float16)v[1]; h[2] = (_Float16)v[2]; h[3] = (_Float16)v[3];
-    *(h16x4*)p = h;
-}
-__global__ __launch_bounds__(256) void bn_stats_h_kernel(const _Float16* __restrict__ x, int64_t ldx, int64_t n, int c,
-                                                         double* __restrict__ partial) {
-    typedef double f64x4 __attribute__((ext_vector_type(4)));
-    column_reduce_staged<1, double>(n, c, partial,
-        [&](int64_t r, int cg, f32x4 (&in)[1]) { in[0] = ldh4(x + r * ldx + cg * 4); },
-        [&](const f32x4 (&in)[1], f64x4& a, f64x4& b) { a = __builtin_convertvector(in[0], f64x4); b = a * a; });
-}
-extern "C" int b2m_bn_stats_h(const void* x, int64_t ldx, int64_t n, int32_t c, double* partial, double* stats, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(x && partial && stats && c > 0 && c % 4 == 0 && c <= 1024 && ldx % 4 == 0 && ldx >= c && n >= 1,
-                  "c and ldx must be multiples of 4, c <= 1024");
-    B2M_CHECK_ARG(((uintptr_t)x % 8) == 0, "x must be 8-byte aligned");
-    const int nblk = reduce_blocks(n);
-    const int c4 = c / 4, nslots = 256 / c4;
-    bn_stats_h_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(double), st>>>((const _Float16*)x, ldx, n, c, partial);
-    reduce_final_kernel<<<2 * c, 64, 0, st>>>(partial, nblk, 2 * c, stats, nullptr, nullptr);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-// statistics + finalize of a half tensor in two launches (b2m_bn_stats_finalize's half twin)
-extern "C" int b2m_bn_stats_finalize_h(const void* x, int64_t ldx, int64_t n, int32_t c, double* partial, const float* gamma,
-                                       const float* beta, float eps, float momentum, float* running_mean, float* running_var,
-                                       float* mean, float* invstd, float* scale, float* shift, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(x && partial && scale && shift && c > 0 && c % 4 == 0 && c <= 1024 && ldx % 4 == 0 && ldx >= c && n >= 1,
-                  "c and ldx must be multiples of 4, c <= 1024");
-    B2M_CHECK_ARG(((uintptr_t)x % 8) == 0, "x must be 8-byte aligned");
-    const int nblk = reduce_blocks(n);
-    const int c4 = c / 4, nslots = 256 / c4;
-    bn_stats_h_kernel<<<nblk, 256, (size_t)nslots * c4 * 8 * sizeof(double), st>>>((const _Float16*)x, ldx, n, c, partial);
-    bn_final_finalize_kernel<<<c, 64, 0, st>>>(partial, nblk, (double)n, c, gamma, beta, eps, momentum, running_mean, running_var,
-                                               mean, invstd, scale, shift, nullptr);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-__global__ __launch_bounds__(256) void bn_apply_h_kernel(const _Float16* __restrict__ x, int64_t ldx, int64_t n, int c4,
-                                                         const float* __restrict__ scale, const float* __restrict__ shift,
-                                                         const _Float16* __restrict__ res, int64_t ldr, int relu,
-                                                         _Float16* __restrict__ y, int64_t ldy) {
-    const int nslots = 256 / c4;
-    const int cg = threadIdx.x % c4, rs = threadIdx.x / c4;
-    if (rs >= nslots) return;
-    const f32x4 s = *(const f32x4*)(scale + cg * 4), b = *(const f32x4*)(shift + cg * 4);
-    for (int64_t r = (int64_t)blockIdx.x * nslots + rs; r < n; r += (int64_t)gridDim.x * nslots) {
-        f32x4 v = ldh4(x + r * ldx + cg * 4);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = __builtin_fmaf(v[u], s[u], b[u]);
-        if (res) v += ldh4(res + r * ldr + cg * 4);
-        if (relu) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = v[u] > 0.f ? v[u] : 0.f;
-        }
-        sth4(y + r * ldy + cg * 4, v);
-    }
-}
-extern "C" int b2m_bn_apply_h(const void* x, int64_t ldx, int64_t n, int32_t c, const float* scale, const float* shift,
-                              const void* residual, int64_t ldr, int32_t relu, void* y, int64_t ldy, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(x && y && scale && shift && c > 0 && c % 4 == 0 && c <= 1024 && ldx % 4 == 0 && ldy % 4 == 0 &&
-                      (!residual || ldr % 4 == 0), "c and leading dimensions must be multiples of 4, c <= 1024");
-    B2M_CHECK_ARG(((uintptr_t)x % 8) == 0 && ((uintptr_t)y % 8) == 0 && ((uintptr_t)residual % 8) == 0, "8-byte aligned rows");
-    if (n == 0) return B2M_OK;
-    bn_apply_h_kernel<<<row_grid(n, c / 4), 256, 0, st>>>((const _Float16*)x, ldx, n, c / 4, scale, shift,
-                                                          (const _Float16*)residual, ldr, relu, (_Float16*)y, ldy);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-// HASY = false (ReLU without a fused residual): the mask is the sign of the forward's fmaf(x, scale, shift), recomputed from the x
-// the kernel reads anyway -- one tensor read less, and the forward need not keep y (as the fp32 kernels do since round 2; a value that
-// underflowed to zero in binary16, |v| < 3e-8, counts as positive here: the derivative of the unrounded function).
-template <bool RELU, bool HASY>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_h_kernel(const _Float16* __restrict__ dy, int64_t lddy,
-                                                              const _Float16* __restrict__ y, int64_t ldy,
-                                                              const _Float16* __restrict__ x, int64_t ldx, int64_t n, int c,
-                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                              const float* __restrict__ mscale, const float* __restrict__ mshift,
-                                                              double* __restrict__ partial) {
-    const int c4 = c >> 2, mycg = (threadIdx.x % c4) * 4;
-    const f32x4 m = *(const f32x4*)(mean + mycg), is = *(const f32x4*)(invstd + mycg);
-    f32x4 ms = {0.f, 0.f, 0.f, 0.f}, mb = {0.f, 0.f, 0.f, 0.f};
-    if (RELU && !HASY) { ms = *(const f32x4*)(mscale + mycg); mb = *(const f32x4*)(mshift + mycg); }
-    constexpr int NIN = (RELU && HASY) ? 3 : 2;
-    column_reduce_staged<NIN>(n, c, partial,
-        [&](int64_t r, int cg, f32x4 (&in)[NIN]) {
-            in[0] = ldh4(dy + r * lddy + cg * 4);
-            in[1] = ldh4(x + r * ldx + cg * 4);
-            if constexpr (RELU && HASY) in[2] = ldh4(y + r * ldy + cg * 4);
-        },
-        [&](const f32x4 (&in)[NIN], f32x4& a, f32x4& b) {
-            f32x4 g = in[0];
-            if constexpr (RELU) {
-                f32x4 yy;
-                if constexpr (HASY) yy = in[NIN - 1];
-                else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) yy[u] = __builtin_fmaf(in[1][u], ms[u], mb[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) g[u] = yy[u] > 0.f ? g[u] : 0.f;
-            }
-            a = g; b = g * ((in[1] - m) * is);
-        });
-}
-extern "C" int b2m_bn_bwd_reduce_h(const void* dy, int64_t lddy, const void* y, int64_t ldy, const void* x, int64_t ldx,
-                                   int64_t n, int32_t c, const float* mean, const float* invstd, int32_t relu,
-                                   const float* mask_scale, const float* mask_shift, double* partial,
-                                   double* sums, float* dbeta_f32, float* dgamma_f32, float param_grad_scale, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(dy && x && mean && invstd && partial && sums && (!relu || y || (mask_scale && mask_shift)),
-                  "NULL argument (relu needs y, or mask_scale and mask_shift)");
-    B2M_CHECK_ARG(c > 0 && c % 4 == 0 && c <= 1024 && lddy % 4 == 0 && ldx % 4 == 0 && (!relu || !y || ldy % 4 == 0) && n >= 1,
-                  "c and leading dimensions must be multiples of 4");
-    B2M_CHECK_ARG(((uintptr_t)dy % 8) == 0 && ((uintptr_t)x % 8) == 0 && ((uintptr_t)y % 8) == 0, "8-byte aligned rows");
-    const int nblk = reduce_blocks(n);
-    const int c4 = c / 4, nslots = 256 / c4;
-    const size_t lds = (size_t)nslots * c4 * 8 * sizeof(float);
-    if (relu && y) bn_bwd_reduce_h_kernel<true, true><<<nblk, 256, lds, st>>>((const _Float16*)dy, lddy, (const _Float16*)y, ldy, (const _Float16*)x, ldx, n, c, mean, invstd, nullptr, nullptr, partial);
-    else if (relu) bn_bwd_reduce_h_kernel<true, false><<<nblk, 256, lds, st>>>((const _Float16*)dy, lddy, nullptr, 0, (const _Float16*)x, ldx, n, c, mean, invstd, mask_scale, mask_shift, partial);
-    else bn_bwd_reduce_h_kernel<false, false><<<nblk, 256, lds, st>>>((const _Float16*)dy, lddy, nullptr, 0, (const _Float16*)x, ldx, n, c, mean, invstd, nullptr, nullptr, partial);
-    reduce_final_kernel<<<2 * c, 64, 0, st>>>(partial, nblk, 2 * c, sums, dbeta_f32, dgamma_f32, param_grad_scale);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-__global__ __launch_bounds__(256) void bn_bwd_apply_h_kernel(const _Float16* __restrict__ dy, int64_t lddy,
-                                                             const _Float16* __restrict__ y, int64_t ldy,
-                                                             const _Float16* __restrict__ x, int64_t ldx, int64_t n, int c,
-                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                             const float* __restrict__ gamma, const double* __restrict__ sums,
-                                                             double count_host, const double* __restrict__ count_dev, int relu,
-                                                             const float* __restrict__ mscale, const float* __restrict__ mshift,
-                                                             _Float16* __restrict__ dx, int64_t lddx,
-                                                             _Float16* __restrict__ dres, int64_t lddres) {
-    const int c4 = c >> 2;
-    const float inv_n = (float)(1.0 / (count_dev ? *count_dev : count_host));
-    const int nslots = 256 / c4;
-    const int cg = threadIdx.x % c4, rs = threadIdx.x / c4;
-    if (rs >= nslots) return;
-    const f32x4 m = *(const f32x4*)(mean + cg * 4), is = *(const f32x4*)(invstd + cg * 4);
-    f32x4 sg, sgx, ga;
-    f32x4 msc = {0.f, 0.f, 0.f, 0.f}, msh = {0.f, 0.f, 0.f, 0.f};
-    if (relu && !y) { msc = *(const f32x4*)(mscale + cg * 4); msh = *(const f32x4*)(mshift + cg * 4); }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        sg[u] = (float)sums[cg * 4 + u] * inv_n; sgx[u] = (float)sums[c + cg * 4 + u] * inv_n;
-        ga[u] = (gamma ? gamma[cg * 4 + u] : 1.f) * is[u];
-    }
-    for (int64_t r = (int64_t)blockIdx.x * nslots + rs; r < n; r += (int64_t)gridDim.x * nslots) {
-        f32x4 g = ldh4(dy + r * lddy + cg * 4);
-        const f32x4 xx = ldh4(x + r * ldx + cg * 4);
-        if (relu) {
-            f32x4 yy;
-            if (y) yy = ldh4(y + r * ldy + cg * 4);
-            else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) yy[u] = __builtin_fmaf(xx[u], msc[u], msh[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) g[u] = yy[u] > 0.f ? g[u] : 0.f;
-        }
-        f32x4 out;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float xh = (xx[u] - m[u]) * is[u];
-            out[u] = ga[u] * (g[u] - sg[u] - xh * sgx[u]);
-        }
-        sth4(dx + r * lddx + cg * 4, out);
-        if (dres) sth4(dres + r * lddres + cg * 4, g);
-    }
 }
 extern "C" int b2m_bn_bwd_apply_h(const void* dy, int64_t lddy, const void* y, int64_t ldy, const void* x, int64_t ldx, int64_t n,
                                   int32_t c, const float* mean, const float* invstd, const float* gamma, const double* sums,
                                   double count, const double* count_dev, int32_t relu, const float* mask_scale,
                                   const float* mask_shift, void* dx, int64_t lddx, void* dres, int64_t lddres, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     B2M_CHECK_ARG(dy && x && mean && invstd && sums && dx && (!relu || y || (mask_scale && mask_shift)),
                   "NULL argument (relu needs y, or mask_scale and mask_shift)");
     B2M_CHECK_ARG(c > 0 && c % 4 == 0 && c <= 1024 && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && (!relu || !y || ldy % 4 == 0) &&
@@ -750,9 +637,9 @@ extern "C" int b2m_bn_bwd_apply_h(const void* dy, int64_t lddy, const void* y, i
     B2M_CHECK_ARG(((uintptr_t)dy % 8) == 0 && ((uintptr_t)x % 8) == 0 && ((uintptr_t)y % 8) == 0 && ((uintptr_t)dx % 8) == 0 &&
                       ((uintptr_t)dres % 8) == 0, "8-byte aligned rows");
     if (n == 0) return B2M_OK;
-    bn_bwd_apply_h_kernel<<<row_grid(n, c / 4), 256, 0, st>>>((const _Float16*)dy, lddy, (const _Float16*)y, ldy, (const _Float16*)x, ldx,
-                                                              n, c, mean, invstd, gamma, sums, count, count_dev, relu,
-                                                              mask_scale, mask_shift, (_Float16*)dx, lddx, (_Float16*)dres, lddres);
+    launch_bn_bwd_apply((const _Float16*)dy, lddy, (const _Float16*)y, ldy, (const _Float16*)x, ldx, n, c, mean, invstd, gamma,
+                        sums, count, count_dev, relu, mask_scale, mask_shift, (_Float16*)dx, lddx, (_Float16*)dres, lddres,
+                        (hipStream_t)stream);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }
@@ -798,9 +685,9 @@ extern "C" int b2m_bn_apply2(const float* xa, int64_t lda, const float* xb, int6
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }
-// backward reduction of the pair: partial[blk][3c] = (sum g, sum g*xhat_a, sum g*xhat_b), g = dy * (y > 0 if relu).
-// Same thread -> (column group, row slot) mapping, row ranges and summation order as column_reduce_staged, so the first two
-// sums are bit for bit those of bn_bwd_reduce_kernel on (dy, y, x_a).
+// backward reduction of the pair: partial[blk][3c] = (sum g, sum g*xhat_a, sum g*xhat_b), g = dy * (y > 0 if relu).  The skeleton
+// with three sums: thread mapping, row ranges and summation order are bn_bwd_reduce_kernel's, so the first two sums are bit for
+// bit those of that kernel on (dy, y, x_a).
 __global__ __launch_bounds__(256) void bn_bwd_reduce2_kernel(const float* __restrict__ dy, int64_t lddy,
                                                              const float* __restrict__ y, int64_t ldy,
                                                              const float* __restrict__ xa, int64_t lda,
@@ -808,59 +695,24 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce2_kernel(const float* __rest
                                                              const float* __restrict__ mean_a, const float* __restrict__ invstd_a,
                                                              const float* __restrict__ mean_b, const float* __restrict__ invstd_b,
                                                              int relu, double* __restrict__ partial) {
-    extern __shared__ float red[];             // [nslots][c4][12]
-    const int c4 = c >> 2;
-    const int nslots = 256 / c4;
-    const int cg = threadIdx.x % c4, rs = threadIdx.x / c4;
-    const int64_t rows_per_blk = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_blk;
-    int64_t r1 = r0 + rows_per_blk;
-    if (r1 > n) r1 = n;
-    f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0}, s2 = {0, 0, 0, 0};
-    if (rs < nslots) {
-        const f32x4 ma = *(const f32x4*)(mean_a + cg * 4), ia = *(const f32x4*)(invstd_a + cg * 4);
-        const f32x4 mb = *(const f32x4*)(mean_b + cg * 4), ib = *(const f32x4*)(invstd_b + cg * 4);
-        auto term = [&](const f32x4& g0, const f32x4& yy, const f32x4& va, const f32x4& vb) {
-            f32x4 g = g0;
+    const int c4 = c >> 2, mycg = (threadIdx.x % c4) * 4;
+    const f32x4 ma = *(const f32x4*)(mean_a + mycg), ia = *(const f32x4*)(invstd_a + mycg);
+    const f32x4 mb = *(const f32x4*)(mean_b + mycg), ib = *(const f32x4*)(invstd_b + mycg);
+    column_reduce_staged<4, float, 3>(n, c, partial,
+        [&](int64_t r, int cg, f32x4 (&in)[4]) {
+            in[0] = *(const f32x4*)(dy + r * lddy + cg * 4);
+            in[1] = *(const f32x4*)(y + r * ldy + cg * 4);
+            in[2] = *(const f32x4*)(xa + r * lda + cg * 4);
+            in[3] = *(const f32x4*)(xb + r * ldb + cg * 4);
+        },
+        [&](const f32x4 (&in)[4], f32x4& a, f32x4& b, f32x4& cc) {
+            f32x4 g = in[0];
             if (relu) {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) g[u] = yy[u] > 0.f ? g[u] : 0.f;
+                for (int u = 0; u < 4; ++u) g[u] = in[1][u] > 0.f ? g[u] : 0.f;
             }
-            s0 += g; s1 += g * ((va - ma) * ia); s2 += g * ((vb - mb) * ib);
-        };
-        int64_t r = r0 + rs;
-        for (; r + 3 * nslots < r1; r += 4 * nslots) {
-            f32x4 in[4][4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t rr = r + (int64_t)u * nslots;
-                in[u][0] = *(const f32x4*)(dy + rr * lddy + cg * 4);
-                in[u][1] = *(const f32x4*)(y + rr * ldy + cg * 4);
-                in[u][2] = *(const f32x4*)(xa + rr * lda + cg * 4);
-                in[u][3] = *(const f32x4*)(xb + rr * ldb + cg * 4);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) term(in[u][0], in[u][1], in[u][2], in[u][3]);
-        }
-        for (; r < r1; r += nslots)
-            term(*(const f32x4*)(dy + r * lddy + cg * 4), *(const f32x4*)(y + r * ldy + cg * 4),
-                 *(const f32x4*)(xa + r * lda + cg * 4), *(const f32x4*)(xb + r * ldb + cg * 4));
-        float* p = red + ((size_t)rs * c4 + cg) * 12;
-        *(f32x4*)p = s0; *(f32x4*)(p + 4) = s1; *(f32x4*)(p + 8) = s2;
-    }
-    __syncthreads();
-    if (rs == 0) {
-        double d[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int s_ = 0; s_ < nslots; ++s_) {
-            const float* p = red + ((size_t)s_ * c4 + cg) * 12;
-#pragma unroll
-            for (int u = 0; u < 12; ++u) d[u] += (double)p[u];
-        }
-        double* o = partial + (size_t)blockIdx.x * 3 * c;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { o[cg * 4 + u] = d[u]; o[c + cg * 4 + u] = d[4 + u]; o[2 * c + cg * 4 + u] = d[8 + u]; }
-    }
+            a = g; b = g * ((in[2] - ma) * ia); cc = g * ((in[3] - mb) * ib);
+        });
 }
 extern "C" int b2m_bn_bwd_reduce2(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* xa, int64_t lda,
                                   const float* xb, int64_t ldb, int64_t n, int32_t c, const float* mean_a,
@@ -871,8 +723,7 @@ extern "C" int b2m_bn_bwd_reduce2(const float* dy, int64_t lddy, const float* y,
     B2M_CHECK_ARG(c > 0 && c % 4 == 0 && c <= 1024 && lddy % 4 == 0 && ldy % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0,
                   "c and leading dimensions must be multiples of 4");
     const int nblk = reduce_blocks(n);
-    const int c4 = c / 4, nslots = 256 / c4;
-    bn_bwd_reduce2_kernel<<<nblk, 256, (size_t)nslots * c4 * 12 * sizeof(float), st>>>(dy, lddy, y, ldy, xa, lda, xb, ldb, n, c,
+    bn_bwd_reduce2_kernel<<<nblk, 256, reduce_lds(c, 3, sizeof(float)), st>>>(dy, lddy, y, ldy, xa, lda, xb, ldb, n, c,
         mean_a, invstd_a, mean_b, invstd_b, relu, partial);
     reduce_final_kernel<<<3 * c, 64, 0, st>>>(partial, nblk, 3 * c, sums, nullptr, nullptr);
     B2M_LAUNCH_CHECK();

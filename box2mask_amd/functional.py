@@ -760,6 +760,68 @@ def merge_bn_sums(local_sums: torch.Tensor, local_count: float, group=None):
     return packed[:-1], packed[-1:]
 
 
+# ---- the statistics sequence of a training-mode BatchNorm over a large map, shared by _BatchNorm, _BatchNormPair, _BatchNormGroup
+# and half_train._BatchNormH: whose sums (`_own_tile_stats`), this rank's sums (`_bn_local_sums`), then either the one-rank finalize
+# (`_bn_finalize_local`, which does both) or the packed exchange (`_bn_exchange`) and the finalize from the global sums
+# (`_bn_finalize_global`).  x: fp32 or half, unit column stride; `partial`: the caller's buffer of the two-stage reduction; `call`:
+# the calling module's `_call` where that is not this one's (half_train: whoever listens to its launches hears these too).
+def _own_tile_stats(ts, n, c):
+    """The per-tile column sums a convolution left on a tensor, or None where they are not the sums of an [n, c] tensor."""
+    if ts is not None and (ts[0].shape[2] != c or ts[1] != (n + 63) // 64):
+        return None
+    return ts
+
+
+def _bn_consts(gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift):
+    """The argument tail every finalize entry ends in."""
+    return (_ptr(gamma), _ptr(beta), eps, momentum, _ptr(running_mean), _ptr(running_var), _ptr(mean), _ptr(invstd),
+            scale.data_ptr(), shift.data_ptr())
+
+
+def _bn_local_sums(x, ts, c, partial, dst_ptr, call=None):
+    """This rank's (sum x, sum x^2): 2c doubles at dst_ptr -- from the tile sums where there are some (no pass over x), else from x."""
+    call = call or _call
+    if ts is not None:
+        call('b2m_bn_tilestats', ts[0].data_ptr(), ts[1], c, partial.data_ptr(), dst_ptr)
+    else:
+        call('b2m_bn_stats_h' if x.dtype == torch.float16 else 'b2m_bn_stats', x.data_ptr(), x.stride(0), x.shape[0], c,
+              partial.data_ptr(), dst_ptr)
+
+
+def _bn_finalize_local(x, ts, partial, *consts, call=None):
+    """One rank: sums and finalize math in two launches (one for a small tile map).  consts: `_bn_consts(...)`."""
+    n, c = x.shape
+    call = call or _call
+    if ts is not None:
+        call('b2m_bn_tilestats_finalize', ts[0].data_ptr(), ts[1], n, c, partial.data_ptr(), None, *consts)
+    elif x.dtype == torch.float16:
+        call('b2m_bn_stats_finalize_h', x.data_ptr(), x.stride(0), n, c, partial.data_ptr(), *consts)
+    else:
+        call('b2m_bn_stats_finalize', x.data_ptr(), x.stride(0), n, c, partial.data_ptr(), None, *consts)
+
+
+def _bn_exchange(stats, n, group):
+    """SyncBN: the local column sums in `stats` and the local row count (its last slot, filled here) travel in ONE packed all-reduce;
+    returns the global count as a device tensor -- the kernels read it from there (no .item(), no count exchange of its own)."""
+    count_dev = stats[-1:]
+    count_dev.fill_(float(n))
+    _sync_all_reduce(stats, group)
+    return count_dev
+
+
+def _bn_finalize_global(stats_ptr, count_dev, c, *consts, call=None):
+    (call or _call)('b2m_bn_finalize', stats_ptr, 0.0, count_dev.data_ptr(), c, *consts)
+
+
+def _param_grad_slots(beta, gamma, c, dev):
+    """(dbeta, dgamma) in buffers of their own: autograd adopts such a tensor as .grad, a view would be cloned."""
+    dbeta, dgamma = grad_slot(beta), grad_slot(gamma)
+    if dbeta is None or dgamma is None:
+        dbeta = torch.empty(c, dtype=torch.float32, device=dev)
+        dgamma = torch.empty(c, dtype=torch.float32, device=dev)
+    return dbeta, dgamma
+
+
 class _BatchNorm(torch.autograd.Function):
     """y = BN(x) (+residual) (ReLU).  BatchNorm1d over all rows of the batch
     (/root/reference/models/resnet.py:63,66,73-82); residual add + ReLU fused as the epilogue."""
@@ -806,31 +868,15 @@ class _BatchNorm(torch.autograd.Function):
                   y.data_ptr(), y.stride(0))
         elif training:
             partial = torch.empty(2 * c * _RED_BLOCKS, dtype=torch.float64, device=dev)
-            if tile_stats is not None and (tile_stats[0].shape[2] != c or tile_stats[1] != (n + 63) // 64):
-                tile_stats = None                  # not this tensor's sums
+            tile_stats = _own_tile_stats(tile_stats, n, c)
+            consts = _bn_consts(gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift)
             if group is None:
-                if tile_stats is not None:         # the producing convolution left the per-tile column sums: no pass over x
-                    _call('b2m_bn_tilestats_finalize', tile_stats[0].data_ptr(), tile_stats[1], n, c, partial.data_ptr(),
-                          None, _ptr(gamma), _ptr(beta), eps, momentum, _ptr(running_mean), _ptr(running_var),
-                          mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr())
-                else:
-                    _call('b2m_bn_stats_finalize', x.data_ptr(), x.stride(0), n, c, partial.data_ptr(), None, _ptr(gamma),
-                          _ptr(beta), eps, momentum, _ptr(running_mean), _ptr(running_var), mean.data_ptr(),
-                          invstd.data_ptr(), scale.data_ptr(), shift.data_ptr())
+                _bn_finalize_local(x, tile_stats, partial, *consts)
             else:
-                # SyncBN: local column sums and the local row count travel in one packed all-reduce; the global count
-                # is read by the kernels from device memory (no .item(), no per-level count exchange)
                 stats = torch.empty(2 * c + 1, dtype=torch.float64, device=dev)
-                if tile_stats is not None:
-                    _call('b2m_bn_tilestats', tile_stats[0].data_ptr(), tile_stats[1], c, partial.data_ptr(), stats.data_ptr())
-                else:
-                    _call('b2m_bn_stats', x.data_ptr(), x.stride(0), n, c, partial.data_ptr(), stats.data_ptr())
-                stats[2 * c:].fill_(float(n))
-                _sync_all_reduce(stats, group)
-                count_dev = stats[2 * c:]
-                _call('b2m_bn_finalize', stats.data_ptr(), 0.0, count_dev.data_ptr(), c, _ptr(gamma), _ptr(beta), eps,
-                      momentum, _ptr(running_mean), _ptr(running_var), mean.data_ptr(), invstd.data_ptr(),
-                      scale.data_ptr(), shift.data_ptr())
+                _bn_local_sums(x, tile_stats, c, partial, stats.data_ptr())
+                count_dev = _bn_exchange(stats, n, group)
+                _bn_finalize_global(stats.data_ptr(), count_dev, c, *consts)
         else:
             _call('b2m_bn_finalize', None, 1.0, None, c, _ptr(gamma), _ptr(beta), eps, momentum, running_mean.data_ptr(),
                   running_var.data_ptr(), None, None, scale.data_ptr(), shift.data_ptr())
@@ -863,12 +909,14 @@ class _BatchNorm(torch.autograd.Function):
         relu = 1 if ctx.relu else 0
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if (ctx.has_res and ctx.needs_input_grad[8]) else None
+        group = _sync_group() if (ctx.training and ctx.sync) else None
+        small = ctx.training and ctx.small and dy.stride(0) % 4 == 0
         if not ctx.training:
             # eval-mode BN is an affine map: dx = scale * g (mean holds `scale` here)
             g = dy if not relu else dy * (y > 0)
             scale = mean.reshape(1, -1)
             dx = g * scale
-            gres = None if dres is None else (g.clone() if g is dy else g)       # (never the incoming tensor itself)
+            dres = None if dres is None else (g.clone() if g is dy else g)       # (never the incoming tensor itself)
             dgamma = dbeta = None
             if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
                 # y = gamma * x_hat + beta with x_hat = (x - running_mean) / sqrt(running_var + eps): the affine parameters
@@ -876,48 +924,34 @@ class _BatchNorm(torch.autograd.Function):
                 dbeta = g.sum(0)
                 invstd = torch.rsqrt(ctx.eval_var + ctx.eval_eps)
                 dgamma = ((g * x).sum(0) - dbeta * ctx.eval_mean) * invstd
-            return (_own(dx, ctx.src_x), dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
-                    None, None, None, None, None, _own(gres, ctx.src_res), None, None, None, None)
-        # parameter gradients in buffers of their own: autograd adopts such a tensor as .grad, a view would be cloned
-        dbeta, dgamma = grad_slot(beta), grad_slot(gamma)
-        if dbeta is None or dgamma is None:
-            dbeta = torch.empty(c, dtype=torch.float32, device=dev)
-            dgamma = torch.empty(c, dtype=torch.float32, device=dev)
-        group = _sync_group() if ctx.sync else None
-        if ctx.small and dy.stride(0) % 4 == 0 and group is not None and ctx.count_dev is not None:
-            # SyncBN on a small map: reduce (this rank's sums, parameter gradients from them) -> all-reduce -> apply
-            xchg = torch.empty(2 * c, dtype=torch.float64, device=dev)
-            args = (dy.data_ptr(), dy.stride(0), _ptr(y), y.stride(0) if y is not None else 0, x.data_ptr(), x.stride(0), n, c,
-                    mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), relu, _ptr(mscale), _ptr(mshift))
-            _call('b2m_bn_small_bwd_phase', 1, *args, dbeta.data_ptr(), dgamma.data_ptr(), None, 0, None, 0, xchg.data_ptr(), None)
-            _sync_all_reduce(xchg, group)
-            _call('b2m_bn_small_bwd_phase', 2, *args, None, None, dx.data_ptr(), dx.stride(0), _ptr(dres),
-                  dres.stride(0) if dres is not None else 0, xchg.data_ptr(), ctx.count_dev.data_ptr())
-            return (_own(dx, ctx.src_x), dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
-                    None, None, None, None, None, _own(dres, ctx.src_res), None, None, None, None)
-        if ctx.small and dy.stride(0) % 4 == 0 and group is None:
-            _call('b2m_bn_small_bwd', dy.data_ptr(), dy.stride(0), _ptr(y), y.stride(0) if y is not None else 0, x.data_ptr(),
-                  x.stride(0), n, c, mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), relu, _ptr(mscale), _ptr(mshift),
-                  dbeta.data_ptr(), dgamma.data_ptr(), dx.data_ptr(), dx.stride(0), _ptr(dres),
-                  dres.stride(0) if dres is not None else 0)
-            return (_own(dx, ctx.src_x), dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
-                    None, None, None, None, None, _own(dres, ctx.src_res), None, None, None, None)
-        partial = torch.empty(2 * c * _RED_BLOCKS, dtype=torch.float64, device=dev)
-        sums = torch.empty(2 * c, dtype=torch.float64, device=dev)
-        _call('b2m_bn_bwd_reduce', dy.data_ptr(), dy.stride(0), _ptr(y), y.stride(0) if y is not None else 0,
-              x.data_ptr(), x.stride(0), n, c, mean.data_ptr(), invstd.data_ptr(), relu, _ptr(mscale), _ptr(mshift),
-              partial.data_ptr(), sums.data_ptr(), dbeta.data_ptr(), dgamma.data_ptr())
-        gsums, count = sums, ctx.count
-        group = _sync_group() if ctx.sync else None
-        if group is not None:
-            gsums = sums.clone()
-            _sync_all_reduce(gsums, group)
-        _call('b2m_bn_bwd_apply', dy.data_ptr(), dy.stride(0), _ptr(y), y.stride(0) if y is not None else 0,
-              x.data_ptr(), x.stride(0), n, c, mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), gsums.data_ptr(),
-              count, _ptr(ctx.count_dev), relu, _ptr(mscale), _ptr(mshift), dx.data_ptr(), dx.stride(0), _ptr(dres),
-              dres.stride(0) if dres is not None else 0)
-        return (_own(dx, ctx.src_x), dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
-                None, None, None, None, None, _own(dres, ctx.src_res), None, None, None, None)
+        else:
+            dbeta, dgamma = _param_grad_slots(beta, gamma, c, dev)
+            tensors = (dy.data_ptr(), dy.stride(0), _ptr(y), y.stride(0) if y is not None else 0, x.data_ptr(), x.stride(0), n, c,
+                       mean.data_ptr(), invstd.data_ptr())
+            mask = (relu, _ptr(mscale), _ptr(mshift))
+            out = (dx.data_ptr(), dx.stride(0), _ptr(dres), dres.stride(0) if dres is not None else 0)
+            if small and group is not None and ctx.count_dev is not None:
+                # SyncBN on a small map: reduce (this rank's sums, parameter gradients from them) -> all-reduce -> apply
+                xchg = torch.empty(2 * c, dtype=torch.float64, device=dev)
+                _call('b2m_bn_small_bwd_phase', 1, *tensors, _ptr(gamma), *mask, dbeta.data_ptr(), dgamma.data_ptr(), None, 0, None, 0,
+                      xchg.data_ptr(), None)
+                _sync_all_reduce(xchg, group)
+                _call('b2m_bn_small_bwd_phase', 2, *tensors, _ptr(gamma), *mask, None, None, *out, xchg.data_ptr(),
+                      ctx.count_dev.data_ptr())
+            elif small and group is None:
+                _call('b2m_bn_small_bwd', *tensors, _ptr(gamma), *mask, dbeta.data_ptr(), dgamma.data_ptr(), *out)
+            else:
+                partial = torch.empty(2 * c * _RED_BLOCKS, dtype=torch.float64, device=dev)
+                sums = torch.empty(2 * c, dtype=torch.float64, device=dev)
+                _call('b2m_bn_bwd_reduce', *tensors, *mask, partial.data_ptr(), sums.data_ptr(), dbeta.data_ptr(), dgamma.data_ptr())
+                gsums = sums
+                if group is not None:
+                    gsums = sums.clone()
+                    _sync_all_reduce(gsums, group)
+                _call('b2m_bn_bwd_apply', *tensors, _ptr(gamma), gsums.data_ptr(), ctx.count, _ptr(ctx.count_dev), *mask, *out)
+        need = ctx.needs_input_grad
+        return (_own(dx, ctx.src_x), dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None, None,
+                _own(dres, ctx.src_res), None, None, None, None)
 
 
 def bn_pair() -> bool:
@@ -948,37 +982,19 @@ class _BatchNormPair(torch.autograd.Function):
             mean_a, inv_a, mean_b, inv_b = f32(), f32(), f32(), f32()
             partial = torch.empty(2 * c * _RED_BLOCKS, dtype=torch.float64, device=dev)
             group = _sync_group() if sync else None
-            sides = ((xa, ga, ba, rma, rva, mom_a, eps_a, mean_a, inv_a, sca, sha, tile_stats_a),
-                     (xb, gb, bb, rmb, rvb, mom_b, eps_b, mean_b, inv_b, scb, shb, tile_stats_b))
+            sides = ((xa, _own_tile_stats(tile_stats_a, n, c), _bn_consts(ga, ba, eps_a, mom_a, rma, rva, mean_a, inv_a, sca, sha)),
+                     (xb, _own_tile_stats(tile_stats_b, n, c), _bn_consts(gb, bb, eps_b, mom_b, rmb, rvb, mean_b, inv_b, scb, shb)))
             if group is None:
-                for x, g, b, rm, rv, mom, eps, mean, inv, sc, sh, ts in sides:
-                    if ts is not None and (ts[0].shape[2] != c or ts[1] != (n + 63) // 64):
-                        ts = None
-                    if ts is not None:
-                        _call('b2m_bn_tilestats_finalize', ts[0].data_ptr(), ts[1], n, c, partial.data_ptr(), None, _ptr(g),
-                              _ptr(b), eps, mom, _ptr(rm), _ptr(rv), mean.data_ptr(), inv.data_ptr(), sc.data_ptr(),
-                              sh.data_ptr())
-                    else:
-                        _call('b2m_bn_stats_finalize', x.data_ptr(), x.stride(0), n, c, partial.data_ptr(), None, _ptr(g),
-                              _ptr(b), eps, mom, _ptr(rm), _ptr(rv), mean.data_ptr(), inv.data_ptr(), sc.data_ptr(),
-                              sh.data_ptr())
+                for x, ts, consts in sides:
+                    _bn_finalize_local(x, ts, partial, *consts)
             else:
                 # SyncBN: the local column sums of BOTH layers and the local row count in one packed all-reduce
                 stats = torch.empty(4 * c + 1, dtype=torch.float64, device=dev)
-                for j, (x, g, b, rm, rv, mom, eps, mean, inv, sc, sh, ts) in enumerate(sides):
-                    if ts is not None and (ts[0].shape[2] != c or ts[1] != (n + 63) // 64):
-                        ts = None
-                    dst = stats.data_ptr() + 8 * 2 * c * j
-                    if ts is not None:
-                        _call('b2m_bn_tilestats', ts[0].data_ptr(), ts[1], c, partial.data_ptr(), dst)
-                    else:
-                        _call('b2m_bn_stats', x.data_ptr(), x.stride(0), n, c, partial.data_ptr(), dst)
-                stats[4 * c:].fill_(float(n))
-                _sync_all_reduce(stats, group)
-                count_dev = stats[4 * c:]
-                for j, (x, g, b, rm, rv, mom, eps, mean, inv, sc, sh, ts) in enumerate(sides):
-                    _call('b2m_bn_finalize', stats.data_ptr() + 8 * 2 * c * j, 0.0, count_dev.data_ptr(), c, _ptr(g), _ptr(b),
-                          eps, mom, _ptr(rm), _ptr(rv), mean.data_ptr(), inv.data_ptr(), sc.data_ptr(), sh.data_ptr())
+                for j, (x, ts, consts) in enumerate(sides):
+                    _bn_local_sums(x, ts, c, partial, stats.data_ptr() + 8 * 2 * c * j)
+                count_dev = _bn_exchange(stats, n, group)
+                for j, (_, _, consts) in enumerate(sides):
+                    _bn_finalize_global(stats.data_ptr() + 8 * 2 * c * j, count_dev, c, *consts)
         else:
             _call('b2m_bn_finalize', None, 1.0, None, c, _ptr(ga), _ptr(ba), eps_a, mom_a, rma.data_ptr(), rva.data_ptr(),
                   None, None, sca.data_ptr(), sha.data_ptr())
@@ -1018,15 +1034,8 @@ class _BatchNormPair(torch.autograd.Function):
         dxa, dxb = torch.empty_like(xa), torch.empty_like(xb)
         partial = torch.empty(3 * c * _RED_BLOCKS, dtype=torch.float64, device=dev)
         sums = torch.empty(3 * c, dtype=torch.float64, device=dev)
-
-        def slots(beta, gamma):
-            db, dg = grad_slot(beta), grad_slot(gamma)
-            if db is None or dg is None:
-                db = torch.empty(c, dtype=torch.float32, device=dev)
-                dg = torch.empty(c, dtype=torch.float32, device=dev)
-            return db, dg
-        dba, dga = slots(ba, ga)
-        dbb, dgb = slots(bb, gb)
+        dba, dga = _param_grad_slots(ba, ga, c, dev)
+        dbb, dgb = _param_grad_slots(bb, gb, c, dev)
         _call('b2m_bn_bwd_reduce2', dy.data_ptr(), dy.stride(0), y.data_ptr(), y.stride(0), xa.data_ptr(), xa.stride(0),
               xb.data_ptr(), xb.stride(0), n, c, mean_a.data_ptr(), inv_a.data_ptr(), mean_b.data_ptr(), inv_b.data_ptr(),
               relu, partial.data_ptr(), sums.data_ptr())
@@ -1076,18 +1085,16 @@ class _BatchNormGroup(torch.autograd.Function):
         stats = torch.empty(off[-1] + 1, dtype=torch.float64, device=dev)
         partial = torch.empty(2 * max(cs) * _RED_BLOCKS, dtype=torch.float64, device=dev)
         for j, x in enumerate(xs):
-            _call('b2m_bn_stats', x.data_ptr(), x.stride(0), n, cs[j], partial.data_ptr(), stats.data_ptr() + 8 * off[j])
-        stats[off[-1]:].fill_(float(n))
-        _sync_all_reduce(stats, group)
-        count_dev = stats[off[-1]:]
+            _bn_local_sums(x, None, cs[j], partial, stats.data_ptr() + 8 * off[j])
+        count_dev = _bn_exchange(stats, n, group)
         ys, saved = [], []
         for j, x in enumerate(xs):
             _, gamma, beta, rm, rv, mom, eps = mem[j]
             c = cs[j]
             f32 = lambda: torch.empty(c, dtype=torch.float32, device=dev)
             mean, invstd, scale, shift = f32(), f32(), f32(), f32()
-            _call('b2m_bn_finalize', stats.data_ptr() + 8 * off[j], 0.0, count_dev.data_ptr(), c, _ptr(gamma), _ptr(beta), eps, mom,
-                  _ptr(rm), _ptr(rv), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr())
+            _bn_finalize_global(stats.data_ptr() + 8 * off[j], count_dev, c,
+                                *_bn_consts(gamma, beta, eps, mom, rm, rv, mean, invstd, scale, shift))
             y = torch.empty_like(x)
             _call('b2m_bn_apply', x.data_ptr(), x.stride(0), n, c, scale.data_ptr(), shift.data_ptr(), None, 0, 0, y.data_ptr(), y.stride(0))
             ys.append(y)
@@ -1109,10 +1116,7 @@ class _BatchNormGroup(torch.autograd.Function):
         for j in range(m):
             x, gamma, beta, mean, invstd = sv[5 * j:5 * j + 5]
             c = cs[j]
-            dbeta, dgamma = grad_slot(beta), grad_slot(gamma)
-            if dbeta is None or dgamma is None:
-                dbeta = torch.empty(c, dtype=torch.float32, device=dev)
-                dgamma = torch.empty(c, dtype=torch.float32, device=dev)
+            dbeta, dgamma = _param_grad_slots(beta, gamma, c, dev)
             # (this rank's sums -> its parameter gradients; the gradient all-reduce averages those over the ranks)
             _call('b2m_bn_bwd_reduce', dys[j].data_ptr(), dys[j].stride(0), None, 0, x.data_ptr(), x.stride(0), n, c, mean.data_ptr(),
                   invstd.data_ptr(), 0, None, None, partial.data_ptr(), sums.data_ptr() + 8 * off[j], dbeta.data_ptr(), dgamma.data_ptr())

@@ -297,8 +297,7 @@ class _BatchNormH(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, residual, relu, sync=False, tile_stats=None):
         x = _hc(x)
         n, c = x.shape
-        if tile_stats is not None and (tile_stats[0].shape[2] != c or tile_stats[1] != (n + 63) // 64):
-            tile_stats = None                  # not this tensor's sums
+        tile_stats = F_._own_tile_stats(tile_stats, n, c)
         dev = x.device
         group = F_._sync_group() if sync else None
         if n <= 1 and group is None:
@@ -306,29 +305,18 @@ class _BatchNormH(torch.autograd.Function):
         residual = _hc(residual) if residual is not None else None
         f32 = lambda: torch.empty(c, dtype=torch.float32, device=dev)
         mean, invstd, scale, shift = f32(), f32(), f32(), f32()
+        consts = F_._bn_consts(gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift)
         count_dev = None
         if group is None:
-            if tile_stats is not None:         # the producing convolution left the per-tile column sums: no pass over x
-                _call('b2m_bn_tilestats_finalize', tile_stats[0].data_ptr(), tile_stats[1], n, c, _workspace(c, dev).data_ptr(), None,
-                      _ptr(gamma), _ptr(beta), eps, momentum, _ptr(running_mean), _ptr(running_var), mean.data_ptr(), invstd.data_ptr(),
-                      scale.data_ptr(), shift.data_ptr())
-            else:
-                _call('b2m_bn_stats_finalize_h', x.data_ptr(), x.stride(0), n, c, _workspace(c, dev).data_ptr(), _ptr(gamma), _ptr(beta),
-                      eps, momentum, _ptr(running_mean), _ptr(running_var), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
-                      shift.data_ptr())
+            F_._bn_finalize_local(x, tile_stats, _workspace(c, dev), *consts, call=_call)
         else:
             stats = torch.empty(2 * c + 1, dtype=torch.float64, device=dev)
-            if n > 0 and tile_stats is not None:
-                _call('b2m_bn_tilestats', tile_stats[0].data_ptr(), tile_stats[1], c, _workspace(c, dev).data_ptr(), stats.data_ptr())
-            elif n > 0:
-                _call('b2m_bn_stats_h', x.data_ptr(), x.stride(0), n, c, _workspace(c, dev).data_ptr(), stats.data_ptr())
-            else:
+            if n > 0:
+                F_._bn_local_sums(x, tile_stats, c, _workspace(c, dev), stats.data_ptr(), call=_call)
+            else:                              # (a rank without rows still takes part in the exchange)
                 stats.zero_()
-            stats[2 * c:].fill_(float(n))
-            F_._sync_all_reduce(stats, group)
-            count_dev = stats[2 * c:]
-            _call('b2m_bn_finalize', stats.data_ptr(), 0.0, count_dev.data_ptr(), c, _ptr(gamma), _ptr(beta), eps, momentum,
-                  _ptr(running_mean), _ptr(running_var), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr())
+            count_dev = F_._bn_exchange(stats, n, group)
+            F_._bn_finalize_global(stats.data_ptr(), count_dev, c, *consts, call=_call)
         y = torch.empty_like(x)
         if n > 0:
             _call('b2m_bn_apply_h', x.data_ptr(), x.stride(0), n, c, scale.data_ptr(), shift.data_ptr(), _ptr(residual),
@@ -348,10 +336,7 @@ class _BatchNormH(torch.autograd.Function):
         n, c = x.shape
         dev = x.device
         relu = 1 if ctx.relu else 0
-        dbeta, dgamma = grad_slot(beta), grad_slot(gamma)
-        if dbeta is None or dgamma is None:
-            dbeta = torch.empty(c, dtype=torch.float32, device=dev)
-            dgamma = torch.empty(c, dtype=torch.float32, device=dev)
+        dbeta, dgamma = F_._param_grad_slots(beta, gamma, c, dev)
         sums = torch.empty(2 * c, dtype=torch.float64, device=dev)
         if n > 0:
             _call('b2m_bn_bwd_reduce_h', dy.data_ptr(), dy.stride(0), _ptr(y), y.stride(0) if y is not None else 0, x.data_ptr(),

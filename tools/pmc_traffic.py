@@ -8,13 +8,22 @@ streamed in, one of the same size out; WRITE_SIZE is exact): the ratio is printe
 import collections
 import csv
 import json
+import re
 import sys
 
 
 def load(path):
     by = collections.defaultdict(lambda: [0.0, 0])
     for r in csv.DictReader(open(path)):
-        base = r['Kernel_Name'].replace('void ', '').split('<')[0].split('(')[0]
+        name = r['Kernel_Name'].replace('void ', '')
+        base = name.split('<')[0].split('(')[0]
+        # the BatchNorm row passes are one template over the element type: the binary16 instantiation moves half the bytes per
+        # launch, so it keeps a row of its own (bn_apply_h_kernel) -- demangled, or as rocprofv3 leaves a _Float16 signature
+        m = re.match(r'_Z\d+(bn_\w+?)_kernelIDF16_', name)
+        if m:
+            base = m.group(1) + '_h_kernel'
+        elif base.startswith('bn_') and name[len(base):].startswith('<_Float16'):
+            base = base[:-len('_kernel')] + '_h_kernel'
         if base.startswith('conv_wgrad'):
             base = 'conv_wgrad_kernel'          # plain + flat-pipeline variants: one b2m_conv_wgrad entry
         if base.startswith('conv_fwd') or base.startswith('conv_1x1'):
