@@ -698,15 +698,19 @@ int b2m_aabb_iou(const double* box6, const int32_t* pcls, int32_t k, const doubl
  * itself); a row with >= min_samples neighbours is core; clusters are the connected components of the core rows, numbered in
  * ascending order of their smallest core row; any other row takes the lowest cluster number among its core neighbours, or -1.
  * labels[n] int32; *n_clusters (device int32) = number of clusters.  workspace: b2m_dbscan_workspace(n) bytes (-1: n out of range).
- * n == 0: returns at once, nothing is launched or written (sklearn raises there).  Integer operations and fp64 comparisons only:
- * every run gives the same labels. */
+ * n == 0: returns at once, nothing is launched or written (sklearn raises there).  A row with a NaN or an infinite value
+ * neighbours no row, itself included (its squared distances are NaN or +inf): it is never core and gets -1, whatever min_samples
+ * is (sklearn raises there); it costs time only -- a -inf puts every other row into one cell.  Integer operations and fp64
+ * comparisons only: every run gives the same labels. */
 int64_t b2m_dbscan_workspace(int64_t n);
 int b2m_dbscan(const double* x, int64_t n, int32_t d, double eps, int32_t min_samples, void* workspace, int32_t* labels,
                int32_t* n_clusters, void* stream);
 
 /* Greedy merge of k proposals given as bit rows (bits[k][words], the layout of b2m_mask_pack, words = ceil(n / 64)) in row order:
- * with o = |row| and f = |row & unlabeled|, row r is accepted when sem[r] >= sem_min, not ((double)f / (double)o < ratio) and
- * not (f < min_points) (evaluation.py:181-191 with 3, 0.6, 200); an accepted row writes inst[p] = r + 1 and (sem_out != NULL)
+ * the pad bits above n are zero, as b2m_mask_pack leaves them (a set one would be counted in o).
+ * With o = |row| and f = |row & unlabeled|, row r is accepted when sem[r] >= sem_min, not ((double)f / (double)o < ratio) and
+ * not (f < min_points) (evaluation.py:181-191 with 3, 0.6, 200); an empty row's 0 / 0 is a NaN, which passes the ratio test, so
+ * such a row is accepted when min_points <= 0 (numpy warns and goes on in the same way); an accepted row writes inst[p] = r + 1 and (sem_out != NULL)
  * sem_out[p] = sem[r] at its still unlabeled points and clears them from `unlabeled`.  The call itself starts from inst = -1
  * and every point unlabeled; sem_out is in / out (the caller fills it with the per-point semantics).  accepted[k]: 0 / 1.
  * One launch of one workgroup: the rows are sequential by definition. */

@@ -1,6 +1,6 @@
 """ARKitScenes detection metric on the device (csrc/detbox.hip through box2mask_amd/eval_detection.py) against the fixture taken
 from the reference's ConvexHull / box3d_iou / calc_iou / eval_det (tests/golden/eval_detection.npz), and at a size no fixture is
-committed for against the numpy restatement below.
+committed for against the numpy restatement of tests/_detbox_rule.py.
 
 Measured on an MI355X (the tests print their figures): hull area relative error 2e-16 and vertex-to-boundary distance 0 against
 bounds of 1e-12; IoU max abs error 1.67e-15 (oriented, 59 overlapping pairs) and 2.22e-16 (axis-aligned) against the bound of 1e-9."""
@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+from _detbox_rule import np_area, np_hull          # the numpy restatement (Andrew's monotone chain, shoelace)
 
 pytestmark = pytest.mark.gpu
 IOU_TOL = 1e-9          # set by the issue: an independent fp64 restatement differs from box3d_iou by at most 5.8e-14 over 1 500 pairs
@@ -26,31 +28,6 @@ def _scene(z, s):
     labels = {k: z['s%d_%s' % (s, k)] for k in ('per_instance_bb_centers', 'per_instance_bb_bounds', 'per_instance_bb_rotations',
                                                'per_instance_semantics')}
     return pred, z['s%d_pos' % s].astype(np.float64), labels
-
-
-# ---- numpy restatement (Andrew's monotone chain, shoelace)
-def np_hull(p2):
-    p = np.unique(p2, axis=0)                        # lexicographic (x, y), duplicates removed
-    if len(p) < 3:
-        return p
-
-    def chain(pts):
-        out = []
-        for q in pts.tolist():                       # (python floats: the same IEEE doubles, much faster than numpy scalars)
-            while len(out) >= 2 and ((out[-1][0] - out[-2][0]) * (q[1] - out[-2][1])
-                                     - (out[-1][1] - out[-2][1]) * (q[0] - out[-2][0])) <= 0.0:
-                out.pop()
-            out.append(q)
-        return out
-    lower, upper = chain(p), chain(p[::-1])
-    return np.array(lower[:-1] + upper[:-1])
-
-
-def np_area(v):
-    if len(v) < 3:
-        return 0.0
-    x, y = v[:, 0] - v[0, 0], v[:, 1] - v[0, 1]
-    return 0.5 * abs(np.dot(x, np.roll(y, -1)) - np.dot(y, np.roll(x, -1)))
 
 
 def boundary_distance(pts, poly):
