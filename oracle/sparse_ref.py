@@ -188,6 +188,100 @@ def segment_pool(x: torch.Tensor, ids: torch.Tensor, n_seg: int, mode: str = 'av
     return torch.where(arg < n, x.gather(0, arg.clamp(max=n - 1)), out)
 
 
+# ----------------------------------------------------------------------------- binary16 storage (half_train.py's rule)
+def to_binary16(x: torch.Tensor) -> torch.Tensor:
+    """x rounded to IEEE binary16 and back in x's dtype: ONE round-to-nearest-even, subnormals kept, no saturation (past 65520: inf).
+    For fp32 that is `x.half()`.  torch converts an fp64 tensor by way of fp32 -- two roundings, which send 1 + 2^-11 + 2^-30 down to 1
+    instead of up to 1 + 2^-10 -- so fp64 goes through numpy, whose conversion rounds the double itself."""
+    if x.dtype == torch.float64:
+        with np.errstate(over='ignore'):
+            return torch.from_numpy(x.detach().contiguous().numpy().astype(np.float16).astype(np.float64)).reshape(x.shape)
+    return x.half().to(x.dtype)
+
+
+class _Stored(torch.autograd.Function):
+    """forward: x -> to_binary16(x) where `round_forward`, else the identity; backward: g -> to_binary16(g * s) / s."""
+
+    @staticmethod
+    def forward(ctx, x, st, round_forward, kind):
+        ctx.st, ctx.kind = st, kind
+        if not round_forward:
+            return x.view_as(x)
+        st.max_activation = max(st.max_activation, float(x.detach().abs().max()) if x.numel() else 0.0)
+        return to_binary16(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        st = ctx.st
+        gs = g * st.loss_scale
+        m = float(gs.abs().max()) if gs.numel() else 0.0
+        st.max_scaled_gradient = max(st.max_scaled_gradient, m)
+        st.max_scaled_gradient_at[ctx.kind] = max(st.max_scaled_gradient_at.get(ctx.kind, 0.0), m)
+        return to_binary16(gs) / st.loss_scale, None, None, None
+
+
+class HalfStorage:
+    """The storage rule of box2mask_amd/half_train.py for an oracle pass in any arithmetic dtype: a tensor the device keeps in HBM
+    as IEEE binary16 is rounded to binary16 (round to nearest even, subnormals kept, no saturation) at the
+    place the device writes it (`to_binary16`), and converted back; every sum in between stays in the caller's dtype.
+
+    `point(x)`     -- a storage point: forward x -> half(x); backward g -> half(g * s) / s.  The oracle's graph is NOT scaled: s
+                      is a power of two, so rounding "as if scaled by s" is exact -- only the subnormal range and the overflow
+                      threshold of the rounding move, which is all the loss scale does on the device.
+    `weight(w)`    -- the binary16 image of fp32 master weights; the gradient passes through un-rounded.
+    `grad_only(x)` -- forward the identity, backward the same rounding: where the device writes a half gradient that autograd
+                      would otherwise add un-rounded to another one.
+    `count[kind]` counts the storage points hit; `max_activation` / `max_scaled_gradient` are the largest magnitudes that met a
+    rounding (before it), for the saturation head-room."""
+
+    def __init__(self, loss_scale: float = 1024.0):
+        self.loss_scale = float(loss_scale)
+        m, e = np.frexp(self.loss_scale)
+        assert m == 0.5 and self.loss_scale > 0, 'the loss scale is a power of two'
+        self.count = {}
+        self.max_activation = 0.0
+        self.max_scaled_gradient = 0.0
+        self.max_scaled_gradient_at = {}          # the same per kind of point ('grad_only': the gradient-only points)
+
+    def point(self, x, kind='activation'):
+        self.count[kind] = self.count.get(kind, 0) + 1
+        return _Stored.apply(x, self, True, kind)
+
+    def grad_only(self, x):
+        return _Stored.apply(x, self, False, 'grad_only')
+
+    def weight(self, w):
+        """The binary16 image of a layer's fp32 master weights (half_train._HalfImages): what the forward and the data gradient
+        multiply with.  The weight gradient is that of the image, un-rounded, handed to the master weight as it is."""
+        self.count['weight'] = self.count.get('weight', 0) + 1
+        return _StoredWeight.apply(w)
+
+
+class _StoredWeight(torch.autograd.Function):
+    """forward: w -> to_binary16(w); backward: the identity (the gradient of the image is the gradient of the master weight)."""
+
+    @staticmethod
+    def forward(ctx, w):
+        return to_binary16(w)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+class _ScaleGrad(torch.autograd.Function):
+    """identity; the gradient times `factor` (only for the deliberate mistakes of tests/test_half_oracle_rule.py)."""
+
+    @staticmethod
+    def forward(ctx, x, factor):
+        ctx.factor = factor
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.factor, None
+
+
 # ----------------------------------------------------------------------------- coordinate hierarchy
 class Hierarchy:
     """All coordinate maps / kernel maps SelectionNet needs for one batch (8 levels)."""
