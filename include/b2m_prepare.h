@@ -113,7 +113,10 @@ int b2m_seg_mode(const int32_t* seg_of_point, const int32_t* cls, int64_t n_pts,
  * shorter than 2 nodes and NULL pointers are such arguments.  Pointers named *_host are read on the host during the call. ---- */
 
 /* stats[0:3] = column mean, [3:6] = column min, [6:9] = column max, [9:12] = column max of |x| of the (n,3) array x.
- * Fixed-order sums (a function of n alone).  partial: double[256 * 12] scratch. */
+ * Fixed-order sums (a function of n alone).  partial: double[256 * 12] scratch.
+ * A NaN is NOT propagated the way numpy propagates it: it makes the mean of its column NaN, and min, max and max |x| ignore it
+ * (they keep a value only when another compares strictly better, and a NaN never does); a column of nothing but NaN gives
+ * +inf, -inf and 0.  Callers that must refuse non-finite input test the mean. */
 int b2m_aug_stats(const double* x, int64_t n, double* partial, double* stats, void* stream);
 
 /* pos[p] <- (pos[p] - c) M^T + (recentre ? c : 0) + t, with M row-major 3x3, c = c_dev (3 doubles on the device, e.g. the
@@ -138,7 +141,8 @@ int b2m_aug_displace(double* pos, int64_t n, const float* grid, int32_t nx, int3
                      const double* step_host, const double* hi_host, double magnitude, void* stream);
 
 /* normals[v] = normalised sum over the faces f of vertex v, in ascending f, of (p1 - p0) x (p2 - p0); a zero sum becomes
- * (0,0,1).  faces: (n_faces,3) vertex indices; row_ptr[n_vert + 1], face_of[3 * n_faces]: the vertex-to-face CSR. */
+ * (0,0,1), and so does one whose length is NaN (a vertex next to a NaN position).  Entries of face_of and of faces whose
+ * values lie outside their range are skipped.  faces: (n_faces,3) vertex indices; row_ptr[n_vert + 1], face_of[3 * n_faces]: the vertex-to-face CSR. */
 int b2m_aug_vertex_normals(const double* pos, int64_t n_vert, const int64_t* faces, int64_t n_faces, const int64_t* row_ptr,
                            const int64_t* face_of, double* normals, void* stream);
 
@@ -152,6 +156,9 @@ int b2m_aug_colour(double* colors, int64_t n, const double* stats, int32_t flags
 /* compute_bounding_box (scannet.py:321-367) for instance ids in [0, n_inst): per-instance fp64 min / max by 64-bit integer
  * atomics (order independent), semantics of the lowest-index point, centre = (min + max) / 2, bounds = max - centre, cast to
  * float32 where the reference stores them; a second pass for offsets = centre - point, their norms and the radius.
+ * Points whose id lies outside [0, n_inst) contribute to no box and get zero offsets and a zero distance; an id without a point
+ * gets zero rows.  Where an instance's coordinates on an axis are zeros of both signs the SIGN of its zero centre is not part of
+ * the contract (its value is).
  * *missing = number of ids in [0, n_inst) without a point (the ids are not dense).  acc: uint64[8 * n_inst] scratch,
  * centers64: double[3 * n_inst] scratch / out; offsets (n,3), distances (n,) float32. */
 int b2m_inst_boxes(const double* pos, const int64_t* instances, const int64_t* semantics, int64_t n, int64_t n_inst,

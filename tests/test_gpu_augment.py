@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+import _augment_rule as R
+
 pytestmark = pytest.mark.gpu
 
 
@@ -80,6 +82,7 @@ def test_blur_matches_scipy(gold):
                 got = _n(augment.blur_(_d(noise, torch.float32)))
                 assert got.shape == want.shape and got.dtype == np.float32
                 assert np.all(np.abs(got.astype(np.float64) - want) <= np.spacing(np.abs(want))), (name, kind)
+                assert R.same_bits(got, R.blur(noise)), (name, kind, 'the rule of tests/_augment_rule.py, bit for bit')
                 total += want.size
                 diff += int((got != want).sum())
     print('blur: %d of %d elements differ' % (diff, total))
@@ -100,6 +103,7 @@ def test_trilinear_on_the_reference_grid(gold):
                 pos = _d(cur)
                 augment.displace_(pos, _d(blur, torch.float32), lo, step, hi, mag)
                 err = np.abs(_n(pos) - gold[dst]).max()
+                assert R.same_bits(_n(pos), R.displace(cur, blur, lo, step, hi, dims, mag)[0]), (name, kind, 'the rule, bit for bit')
                 worst = max(worst, err / max(1.0, mag))
                 assert err <= 1e-9 * max(1.0, mag), (name, kind, err)
     print('trilinear: worst error / max(1, magnitude) = %.3g' % worst)
@@ -161,16 +165,19 @@ def test_colour_steps(gold, name):
     stages = [(name + '_in', [('auto_contrast', float(gold[name + '_blend']))], name + '_contrast'),
               (name + '_contrast', [('translation', gold[name + '_tr'].reshape(3))], name + '_translation'),
               (name + '_translation', [('jitter', -0.1, 0.1, gold[name + '_jitter'])], name + '_jittered')]
-    for src, steps, dst in stages:
+    rule_args = (float(gold[name + '_blend']), gold[name + '_tr'].reshape(3), gold[name + '_jitter'])
+    for flag, (src, steps, dst) in zip((1, 2, 4), stages):
         got = _n(augment.colour_(_d(gold[src]), steps))
         want = gold[dst]
         assert _ulp_close(got, want, 4), dst
+        assert R.same_bits(got, R.colour(gold[src], R.stats(gold[src])[0], flag, *rule_args)), (dst, 'the rule, bit for bit')
         clipped = (want == 0) | (want == 1)
         assert np.array_equal(got[clipped], want[clipped])
     # the fused pass: all three at once, against the reference's chain
     got = _n(augment.colour_(_d(gold[name + '_in']), [s[1][0] for s in stages]))
     want = gold[name + '_jittered']
     assert _ulp_close(got, want, 4)
+    assert R.same_bits(got, R.colour(gold[name + '_in'], R.stats(gold[name + '_in'])[0], 7, *rule_args)), 'the rule, bit for bit'
     clipped = (want == 0) | (want == 1)
     assert clipped.any() and np.array_equal(got[clipped], want[clipped])
     if name == 'colconst':
@@ -193,6 +200,10 @@ def test_instance_boxes_match_compute_bounding_box(gold):
         got, want = _n(lab[k]), gold['box_' + k]
         assert got.shape == want.shape and got.dtype == np.float32, k
         assert np.all(np.abs(got.astype(np.float64) - want) <= np.spacing(want)), k
+    rule = R.inst_boxes(pos, inst, sem, 9)                                  # ... and the rule's order, bit for bit
+    assert R.same_bits(_n(lab['per_instance_bb_radius']), rule['per_radius'])
+    assert R.same_bits(_n(lab['bb_radius']), rule['per_radius'][inst][:, None])
+    assert R.same_bits(_n(lab['bb_center_distances']), rule['distances'][:, None])
     assert np.array_equal(_n(lab['semantics']), sem) and np.array_equal(_n(lab['instances']), inst) and lab['seg2inst'] is seg2inst
     gappy = inst.copy()
     gappy[gappy == 4] = 3                                                   # ids 0..8 without 4

@@ -64,6 +64,126 @@ def test_tie_cases_do_tie():
     assert ties and (d2[60] == 0).sum() == 21 and NC.brute(ref, q)[0][60] == 0
 
 
+# ---------------------------------------------------------------- the edge cases (tests/test_gpu_neighbors_edges.py runs them)
+EDGE_NO_TIES = [n for n in NC.EDGE_ORDER if not NC.edge_case(n)[2]] + NC.SHELLS
+EDGE_TIES = [n for n in NC.EDGE_ORDER if NC.edge_case(n)[2]]
+
+
+@pytest.mark.parametrize('name', EDGE_NO_TIES)
+def test_edge_cases_are_unambiguous(name):
+    ref, q, _ = NC.edge_case(name)
+    idx, best, second = NC.edge_brute(name)
+    ok_q = np.isfinite(q).all(1)
+    assert ok_q.all() and (idx >= 0).all() and np.isfinite(ref[idx]).all()
+    assert _gap_ok(best, second), 'two candidates within a relative %g' % NC.GAP
+
+
+def test_tie_edge_cases_do_tie():
+    for name in EDGE_TIES:
+        ref, q, _ = NC.edge_case(name)
+        idx, best, second = NC.edge_brute(name)
+        tied = second == best
+        assert tied.any(), name
+        with np.errstate(all='ignore'):
+            d2 = NC.d2_rows(ref, q)
+        d2[:, ~np.isfinite(ref).all(1)] = np.nan
+        low = np.array([np.nonzero(r == b)[0][0] for r, b in zip(d2, best)])
+        assert np.array_equal(low, idx), (name, 'the lowest of the tied rows')
+        if name in ('two_identical', 'all_identical', 'denormal', 'denormal_min'):
+            assert tied.all() and (idx == 0).all(), name
+        if name == 'denormal':
+            assert np.ptp(ref, 0).max() <= 1e-320 and (d2 == d2[:, :1]).all()                    # every row ties for every query
+        if name == 'extent_1e300':
+            assert np.isinf(best[:100]).all() and (idx[:100] == 0).all() and (best[100:] == 0).all()
+            assert np.array_equal(idx[100:], np.arange(100, 150))
+        if name == 'overflow':
+            assert np.isinf(d2[:, 1:]).all() and (idx == 1).all() and np.isnan(ref[0]).any()      # the lowest FINITE row, at +inf
+        if name.startswith('lattice'):
+            m = int(name[7:])
+            n_tied = (d2 == best[:, None]).sum(1)
+            per = (m - 1) ** 3
+            assert np.array_equal(n_tied, np.repeat([2, 2, 2, 4, 4, 4, 8], per)), name
+            # ties across cells: the tied rows of a query lie in different shells around the query's cell
+            grid = NC.grid_of(ref)
+            spread = 0
+            for j in range(len(q)):
+                rows = np.nonzero(d2[j] == best[j])[0]
+                sh = NC.shell_of(np.repeat(q[j:j + 1], len(rows), 0), ref[rows], grid)
+                spread += int(sh.min() != sh.max())
+            assert spread >= len(q) // 10, (name, spread)
+
+
+def test_equidistant_rows_r_and_r_plus_1_cells_away():
+    """Query j of 'equidistant' is exactly half-way between two rows, one j cells from its cell and one j + 1, whatever the last
+    places of the edge; brute force takes the lower row."""
+    ref, q, _ = NC.edge_case('equidistant')
+    idx, best, second = NC.edge_brute('equidistant')
+    d2 = NC.d2_rows(ref, q)
+    assert (second == best).all()
+    for j, r in enumerate(NC.EQUI_R):
+        rows = np.nonzero(d2[j] == best[j])[0]
+        assert len(rows) == 2 and idx[j] == rows[0] and (ref[rows, 1] == q[j, 1]).all()
+        for scale in (1 - 1e-9, 1.0, 1 + 1e-9):
+            sh = NC.shell_of(np.repeat(q[j:j + 1], 2, 0), ref[rows], NC.grid_of(ref, scale))
+            assert sorted(sh.tolist()) == [r, r + 1], (j, sh)
+
+
+@pytest.mark.parametrize('kind', list(NC.SHELL_DIRS))
+def test_shell_cases_put_the_winner_in_shell_r(kind):
+    for r in NC.SHELL_R:
+        ref, q, winner, decoy, s = NC.shell_case(kind, r)
+        idx, best, second = NC.edge_brute('shell:%s:%d' % (kind, r))
+        assert idx[0] == winner, (kind, r)
+        d_decoy = NC.d2_rows(ref[decoy:decoy + 1], q)[0, 0]
+        assert second[0] == d_decoy > best[0] * 1.05 ** 2, (kind, r, 'the decoy is the runner-up, farther than the winner')
+        assert np.ptp(ref, 0).tolist() == [1.0, 1.0, 1.0]
+        for scale in (1 - 1e-9, 1.0, 1 + 1e-9):                                 # (whatever the last places of the device's edge)
+            grid = NC.grid_of(ref, scale)
+            assert grid[3].tolist() == [21, 21, 21]
+            assert NC.shell_of(q, ref[[winner]], grid)[0] == r, (kind, r, scale)
+            assert NC.shell_of(q, ref[[decoy]], grid)[0] == s, (kind, r, scale)
+            # every shell nearer than r holds only farther rows
+            near = NC.shell_of(np.repeat(q, len(ref), 0), ref, grid) < r
+            assert (NC.d2_rows(ref[near], q)[0] > best[0]).all()
+        assert s < r or r == 0, (kind, r, s)
+        assert second[0] > ((r - 1) * grid[2]) ** 2 or r < 2, 'the walk cannot stop at the decoy before it reaches shell r'
+
+
+def test_edge_cases_reach_the_branches_of_the_edge_choice():
+    g = {n: NC.grid_of(NC.edge_case(n)[0]) for n in ('one_row', 'two_identical', 'all_identical', 'denormal', 'extent_1e300', 'growth',
+                                                       'line', 'long_scan', 'only_last_finite')}
+    for n in ('one_row', 'two_identical', 'all_identical', 'only_last_finite'):
+        assert g[n][2] == 1.0 and g[n][3].tolist() == [1, 1, 1], n                 # k = 0: one cell
+    lo, hi, edge, dim = g['denormal']
+    assert (hi - lo).max() / 524288.0 == 0.0 and 0 < edge < (hi - lo).max() <= 1e-320          # `least` underflows, the edge does not
+    lo, hi, edge, dim = NC.grid_of(NC.edge_case('denormal_min')[0])
+    assert edge == (hi - lo).max() == 3 * 5e-324 and dim.tolist() == [2, 2, 2]                  # the edge underflows: the guard
+    lo, hi, edge, dim = g['extent_1e300']
+    assert np.isfinite(edge) and dim.prod() <= 4 * 300 + 8
+    lo, hi, edge, dim = g['growth']
+    ext = hi - lo
+    assert ext.max() / 524288.0 > np.exp(np.log(ext).sum() / 3 - np.log(4000.0) / 3), 'the clip is what sets the first edge'
+    assert edge > 2 * ext.max() / 524288.0 and dim[0] == dim[1] == 1 and 4000 < dim[2] <= 8008, 'and the growth loop has run'
+    lo, hi, edge, dim = g['line']
+    assert edge == (hi - lo).max() / 524288.0 and dim.tolist() == [524289, 1, 1], 'the clip at 2^19 cells per axis'
+    lo, hi, edge, dim = g['long_scan']
+    cells = NC.cell_of(NC.edge_case('long_scan')[0], g['long_scan'])
+    assert (cells[:5000] == 0).all() and dim.min() > 10
+
+
+def test_queries_outside_the_box_and_their_clamped_cells():
+    ref, q, _ = NC.edge_case('outside')
+    idx = NC.edge_brute('outside')[0]
+    grid = NC.grid_of(ref)
+    lo, hi = grid[0], grid[1]
+    n_out = ((q < lo) | (q > hi)).sum(1)
+    assert (n_out >= 1).all() and {1, 2, 3} == set(n_out.tolist())                  # beyond a face, an edge, a corner
+    gap = np.where(q < lo, lo - q, np.where(q > hi, q - hi, 0)).max(1) / (hi - lo).max()      # in box sizes
+    assert gap.min() < 2e-9 and abs(np.median(gap) - 1) < 1e-9 and gap.max() > 999
+    sh = NC.shell_of(q, ref[idx], grid)
+    assert (sh > 0).sum() >= 10 and (sh == 0).any(), 'the nearest row is often not in the clamped cell'
+
+
 # ---------------------------------------------------------------- the fixtures taken from the reference
 def test_labels_fixture_holds_its_cases_and_the_restatement_reproduces_the_reference():
     import _s3dis_full_rule as F
