@@ -28,7 +28,10 @@ def scannet_config(**overrides):
         checkpoint_path='experiments/scannet/checkpoints/', voxel_size=0.02, batch_size=8, lr=1e-3,
         half_inference=False,        # build extension (no reference field): inference on half activations, see model.Model
         half_training=False,         # build extension: training passes with the trunk's activations / gradients in half (half_train.py)
-        half_loss_scale=1024.0,      # ... and the factor its gradients are scaled by inside the half region (a power of two)
+        half_loss_scale=1024.0,      # ... and the factor its gradients are scaled by inside the half region (a power of two), or
+                                     # 'dynamic' (half_guard.py): a step whose gradients overflowed is skipped and halves the scale,
+        half_loss_scale_init=1024.0, # which starts here
+        half_growth_interval=2000,   # and doubles after this many clean steps in a row
         # augmentation (config_loader.py:189-227, read by augment.draw_params; everything off by default as in the reference --
         # configs/scannet.txt switches on augmentation, rotation_90_aug, flipping_aug 0.5, scaling_aug [1, .8, 1.2] and apply_hue_aug,
         # the last of which augment.py refuses)

@@ -179,7 +179,17 @@ class SelectionNet(ResNetBase):
                       torch.is_grad_enabled() and not half)
         if half_train:
             from . import half_train as HT
-            HT.loss_scale[0] = float(getattr(self.cfg, 'half_loss_scale', 1024.0))
+            scale = getattr(self.cfg, 'half_loss_scale', 1024.0)
+            if scale == 'dynamic':
+                # the guard of half_guard.py: the scale of THIS pass is settled by the first backward operator of the region (it
+                # depends on what the previous step found, and nothing here waits for that)
+                HT.guard[0] = getattr(self, '_half_scaler', None)
+                if HT.guard[0] is None:
+                    raise RuntimeError("cfg.half_loss_scale = 'dynamic' needs a half_guard.HalfScaler (model.Model makes one)")
+                HT.loss_scale[0] = HT.guard[0].scale
+            else:
+                HT.guard[0] = None
+                HT.loss_scale[0] = float(scale)
             HT.images.begin_pass()                  # every half weight image of the step in one launch, beside the stem
             out_p1 = out_p1.new(HT.to_half(out_p1.F))
         if half:

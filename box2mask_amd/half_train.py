@@ -15,7 +15,8 @@ stay fp32, as do the weights (master copies, the optimizer's); every accumulatio
   half output where a residual is fused, else the sign of the fp32 fmaf(x, scale, shift) recomputed from x -- y is not kept);
 * loss scaling: the gradient is multiplied by `loss_scale` where it enters the half region (`to_float`), every parameter gradient
   the region produces is multiplied by 1 / loss_scale by the operator that produced it, and the gradient that leaves the region
-  towards the stem (`to_half`) likewise -- outside the region nothing is scaled.
+  towards the stem (`to_half`) likewise -- outside the region nothing is scaled.  The scale is a constant (`cfg.half_loss_scale`, a
+  float) or, with `cfg.half_loss_scale = 'dynamic'`, follows an overflow guard on the device (half_guard.py).
 
 Turned on by `SelectionNet.half_training = True` (or `cfg.half_training`); under data parallelism the BatchNorm takes its SyncBN form
 (one packed exchange per direction, as the fp32 operator) and the fp32 parameter gradients travel as always.  The layers
@@ -36,6 +37,22 @@ _call = _lib.call
 _ptr = _lib.ptr
 
 loss_scale = [1024.0]        # set by SelectionNet.forward from cfg.half_loss_scale (a power of two: scaling is exact)
+guard = [None]               # cfg.half_loss_scale == 'dynamic': the half_guard.HalfScaler of the pass in flight -- every backward operator
+                             # below first lets it set loss_scale[0], then has it scan the half gradients it produced; else None
+
+
+def _begin_backward():
+    if guard[0] is not None:
+        guard[0].begin_backward()
+
+
+def _scan(*grads):
+    """The overflow guard looks at the half gradients an operator has just produced (on this stream, behind the producing launch)."""
+    g = guard[0]
+    if g is not None:
+        for t in grads:
+            if t is not None:
+                g.scan_half(t)
 
 
 def _hc(t):
@@ -227,6 +244,7 @@ class _ConvH(torch.autograd.Function):
         x1, x2, weight = ctx.saved_tensors
         if dy is None:                         # only the passed-through inputs were used downstream
             return p1, p2, None, None, None, None, None, None, None
+        _begin_backward()
         dy = _hc(dy)
         w3 = weight if weight.dim() == 3 else weight.unsqueeze(0)
         K, cin, cout = w3.shape
@@ -241,6 +259,7 @@ class _ConvH(torch.autograd.Function):
             dx1 = _conv_h(dy, None, weight_pack_ht(weight, ctx.mirror, 0, c1), K, ctx.rb_b, x1.shape[0], c1, res=p1 if f else None)
             if p1 is not None and not f:
                 dx1 = dx1 + p1
+            _scan(dx1)
         elif p1 is not None:
             dx1 = p1
         if x2 is not None and ctx.needs_input_grad[1]:
@@ -249,6 +268,7 @@ class _ConvH(torch.autograd.Function):
                           res=p2 if f else None)
             if p2 is not None and not f:
                 dx2 = dx2 + p2
+            _scan(dx2)
         elif p2 is not None:
             dx2 = p2
         if ctx.needs_input_grad[2]:
@@ -332,6 +352,7 @@ class _BatchNormH(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, y, gamma, beta, mean, invstd, mscale, mshift = ctx.saved_tensors
+        _begin_backward()
         dy = _hc(dy)
         n, c = x.shape
         dev = x.device
@@ -354,6 +375,7 @@ class _BatchNormH(torch.autograd.Function):
                   x.stride(0), n, c, mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), sums.data_ptr(), float(n),
                   _ptr(ctx.count_dev) if group is not None else None, relu, _ptr(mscale), _ptr(mshift),
                   dx.data_ptr(), dx.stride(0), _ptr(dres), dres.stride(0) if dres is not None else 0)
+            _scan(dx, dres)
         return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None, None, None, None,
                 None, dres, None, None, None)
 
@@ -373,6 +395,7 @@ class _ToHalf(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _begin_backward()
         return g.float() * (1.0 / loss_scale[0])
 
 
@@ -386,7 +409,10 @@ class _ToFloat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return (g * loss_scale[0]).half()
+        _begin_backward()
+        out = (g * loss_scale[0]).half()
+        _scan(out)
+        return out
 
 
 def to_half(x):

@@ -76,6 +76,14 @@ class Model:
             from . import parallel, functional as F_
             if parallel.syncbn_ipc_enabled() and dist_world() > 1 and F_.ipc_exchange is None:
                 F_.ipc_exchange = parallel.IpcExchange(device=torch.device(device) if device is not None else None)
+        # cfg.half_loss_scale == 'dynamic' (a build extension like half_training): overflow guard + loss-scale policy, half_guard.py
+        self.half_scaler = None
+        if getattr(cfg, 'half_loss_scale', None) == 'dynamic':
+            from .half_guard import HalfScaler
+            self.half_scaler = HalfScaler(init_scale=getattr(cfg, 'half_loss_scale_init', 1024.0),
+                                          growth_interval=getattr(cfg, 'half_growth_interval', 2000), device=device,
+                                          arena=self._arena, dp=self._dp)
+            self.detection_model._half_scaler = self.half_scaler
         self.BCEWithLogitsLoss = torch.nn.BCEWithLogitsLoss().to(device)
         self.semantics_loss = torch.nn.CrossEntropyLoss(ignore_index=-100).to(device)
         self._id2idx_dev = None
@@ -315,6 +323,13 @@ class Model:
 
     def parameters(self):
         return self.detection_model.parameters()
+
+    def attach_optimizer(self, optimizer):
+        """The one call dynamic loss scaling adds to the reference's loop (training.py:63-70 stays as it is): the (fused) optimizer
+        then skips a step whose gradients overflowed.  Without cfg.half_loss_scale == 'dynamic' it does nothing."""
+        if self.half_scaler is not None:
+            self.half_scaler.attach(optimizer)
+        return optimizer
 
     def to(self, device):
         self.detection_model = self.detection_model.to(device)

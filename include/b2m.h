@@ -343,6 +343,24 @@ int b2m_bn_bwd_apply_h(const void* dy, int64_t lddy, const void* y, int64_t ldy,
                        double count, const double* count_dev, int32_t relu, const float* mask_scale, const float* mask_shift,
                        void* dx, int64_t lddx, void* dres, int64_t lddres, void* stream);
 
+/* ---------------------------------------------------------------- overflow guard of half training (box2mask_amd/half_guard.py)
+ * The kernels above leave an overflow behind in three forms: +-inf (b2m_bn_bwd_apply_h, the cast where the gradient enters the
+ * region), NaN, and -- from the data-gradient launches of b2m_conv_fwd_h, whose epilogue clamps -- the finite value +-65504.  The
+ * guard reads what they wrote and folds it into one word per number format:
+ *   b2m_half_absmax   *out = max(*out, max over the n x c binary16 elements of (bits & 0x7fff)); x has row pitch ld >= c (in
+ *                     elements), columns c ... ld-1 are never read, x needs 2-byte alignment only, ld may be odd; n == 0 launches
+ *                     nothing.  n * ld must stay below 2^31 - 2^19 (the kernel counts its work in 32 bits).
+ *   b2m_f32_absmax    the same over n floats with (bits & 0x7fffffff).
+ * Magnitude bits order as unsigned integers: finite < 65504 (0x7bff) < inf (0x7c00) < every NaN (fp32: inf = 0x7f800000), so the
+ * word is the largest gradient, "clipped" and "not finite" at once.  One atomicMax per workgroup; the caller zeroes *out.
+ *   b2m_guard_finish  one thread: found = flags[0] >= 0x7bff || flags[1] >= 0x7f800000 (flags[0]: the half word, flags[1]: the
+ *                     fp32 word); *found_inf = found ? 1.0f : 0.0f (what torch's fused optimizers take as `found_inf`);
+ *                     counters[0] += 1 (steps seen), counters[1] += found (steps skipped).  The flags are left as they are.
+ * All three refuse NULL pointers, negative sizes, ld < c and a size beyond the index range on the host, before any launch. */
+int b2m_half_absmax(const void* x, int64_t ld, int64_t n, int32_t c, uint32_t* out, void* stream);
+int b2m_f32_absmax(const float* g, int64_t n, uint32_t* out, void* stream);
+int b2m_guard_finish(const uint32_t* flags, float* found_inf, uint32_t* counters, void* stream);
+
 /* ---------------------------------------------------------------- SyncBN statistics exchange inside one node (opt-in)
  * Device-side all-reduce (SUM) of n <= b2m_xchg_max_doubles() doubles between <= b2m_xchg_max_ranks() ranks whose MAILBOXES
  * (b2m_xchg_size() bytes of device memory each) are mapped into one another through HIP IPC: one launch of one workgroup

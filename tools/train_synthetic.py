@@ -100,6 +100,9 @@ def main(argv=None):
     ap.add_argument('--eval-every', type=int, default=50)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--half', type=int, default=0, help='1: cfg.half_training (half activations / gradients in the trunk, half_train.py)')
+    ap.add_argument('--loss-scale', default='1024',
+                    help="with --half 1: the constant loss scale (a power of two), or 'dynamic' -- the overflow guard of half_guard.py "
+                         'skips a step whose gradients overflowed and halves the scale')
     ap.add_argument('--metric', choices=['scannet', 'arkit'], default='scannet',
                     help='arkit: the oriented-box detection mAP (eval_detection.py) beside the ScanNet AP')
     ap.add_argument('--augment', action='store_true',
@@ -108,7 +111,8 @@ def main(argv=None):
                     help='keep the checkpoint here (tools/param_search.py reads it); default: a temporary directory')
     args = ap.parse_args(argv)
     torch.manual_seed(args.seed)
-    cfg = scannet_config(lr=args.lr, mlp_bb_scores_start_epoch=0, half_training=bool(args.half))       # score head trained from the first step
+    cfg = scannet_config(lr=args.lr, mlp_bb_scores_start_epoch=0, half_training=bool(args.half),       # score head trained from the first step
+                         half_loss_scale='dynamic' if args.loss_scale == 'dynamic' else float(args.loss_scale))
     if args.checkpoint_dir:
         os.makedirs(args.checkpoint_dir, exist_ok=True)
     cfg.checkpoint_path = (args.checkpoint_dir.rstrip('/') if args.checkpoint_dir else tempfile.mkdtemp(prefix='b2m_ckpt_')) + '/'
@@ -119,6 +123,7 @@ def main(argv=None):
         aug_rng = np.random.default_rng(args.seed)
     model = Model(cfg, *synth.scannet_tables())
     opt = torch.optim.Adam(model.parameters(), lr=cfg.lr, fused=True)
+    model.attach_optimizer(opt)                  # (--loss-scale dynamic: the optimizer skips an overflowed step; else nothing)
     model.train()
     history = []
     t0 = time.time()
@@ -134,6 +139,10 @@ def main(argv=None):
             print('step %4d  loss %.4f  AP50 %.3f  AP25 %.3f  AP %.3f  (%.1f s)'
                   % (step, float(losses['optimization_loss'].detach()), avg['all_ap_50%'], avg['all_ap_25%'], avg['all_ap'],
                      time.time() - t0), flush=True)
+    if model.half_scaler is not None:
+        st = model.half_scaler.stats()
+        print('loss scale %g after %d steps, %d skipped (largest half gradient of the last step %g)'
+              % (st['scale'], st['steps'], st['skipped'], st['max_half_grad']))
     # checkpoint in the reference's format (models/training.py:212-226) and reload through Model.load_checkpoint
     secs = float(int(time.time() - t0))          # the reference names checkpoints by the float training time
     name = 'checkpoint_{}h:{}m:{}s_{}'.format(int(secs // 3600), int((secs // 60) % 60), int(secs % 60), secs)
