@@ -129,6 +129,8 @@ PROTOTYPES = {
     'b2m_aug_displace': [P, I64, P, I32, I32, I32, P, P, P, F64, P],
     'b2m_aug_vertex_normals': [P, I64, P, I64, P, P, P, P],
     'b2m_aug_colour': [P, I64, P, I32, F64, P, P, P],
+    'b2m_aug_colour8': [P, I64, I32, F32, P, P, P, P, P, P, P, P, P],
+    'b2m_aug_brightness': [P, I64, F32, P],
     'b2m_inst_boxes': [P, P, P, I64, I64, P, P, P, P, P, P, P, P, P, P],
     # ... nearest-neighbour index (box2mask_amd/neighbors.py)
     'b2m_nn_build': [P, I64, P, P],

@@ -12,9 +12,12 @@ ever see explicit matrices, centres and grids.  ``instance_labels`` recomputes t
 Pinned to the reference (tests/golden/augment.npz, made by its own functions): the grid blur and the trilinear displacement
 of ``elastic_distortion`` / ``HAIS_elastic`` with their grid dimensions and axes, ``ChromaticAutoContrast``,
 ``ChromaticTranslation``, ``color_jittering`` and ``compute_bounding_box``.  Unpinned (open3d is not available to pin
-them): the conventions of open3d that ``draw_params`` restates, and the vertex normals.  Refused (they need albumentations /
-cv2): ``apply_hue_aug``, ``mix_3d_color_aug``, ``random_brightness``.  The reference's ``np.random`` call stream is not
-replayed: the draws have its distributions, not its sequence.
+them): the conventions of open3d that ``draw_params`` restates, and the vertex normals.  The three colour steps that need
+albumentations / cv2 -- ``apply_hue_aug``, ``mix_3d_color_aug``, ``random_brightness`` -- are refused by default and drawn with
+``draw_params(..., byte_colour=True)``: then they follow the exact rule of profiles/colour8_rule.md (numpy statements for
+the tables and the normalisation, OpenCV's 8-bit colour-space conversions restated in integer / fp32 arithmetic), which is
+UNPINNED too -- neither library is available to check it against; tools/pin_colour8.py pins it where they are.  The
+reference's ``np.random`` call stream is not replayed: the draws have its distributions, not its sequence.
 
 Normals: an affine step maps them by the normalised cofactor matrix, which equals recomputing area-weighted vertex normals
 on the transformed mesh (mirroring included).  After a non-affine step (elastic, hais, jitter) they are recomputed from
@@ -50,6 +53,11 @@ class SceneAugment:
         ('jitter', sigma, seed)      pos <- pos + sigma * randn                                 scannet.py:202-204
     colour: steps in the reference's order
         ('auto_contrast', blend), ('translation', row (3,)), ('jitter', lo, hi, array (P,3) | int seed)
+      and, from draw_params(..., byte_colour=True), the byte-colour steps (plain numbers; profiles/colour8_rule.md)
+        ('brightness', beta)                                              random_brightness, augmentation.py:63-66
+        ('mix3d', alpha, beta, (r, g, b) shifts)                          apply_mix3d_color_aug, :148-156
+        ('hue', hue_shift, sat_shift, val_shift, alpha, beta, (r, g, b) shifts)     apply_hue_aug, :158-168
+      'mix3d' and 'hue' leave normalised float32 values (negative and above 1); they exclude each other.
     """
     geometric: list = field(default_factory=list)
     colour: list = field(default_factory=list)
@@ -64,7 +72,14 @@ def _rot_xyz(ax, ay, az):
     return rx @ ry @ rz
 
 
-def draw_params(cfg, n_points_hint=None, generator=None) -> SceneAugment:
+COLOR_MEAN = (0.47793125906962, 0.4303257521323044, 0.3749598901421883)     # augmentation.py:12-13
+COLOR_STD = (0.2834475483823543, 0.27566157565723015, 0.27018971370874995)
+HUE_LIMITS = (50.0, 60.0, 50.0)                                             # hue, sat, val shift limits (augmentation.py:19-21)
+MIX3D_LIMITS = (0.2, 0.2, 20.0)                                             # contrast, brightness, RGB shift (the Mix3D yaml)
+_COLOUR_ORDER = ('auto_contrast', 'translation', 'jitter', 'brightness', 'mix3d', 'hue')
+
+
+def draw_params(cfg, n_points_hint=None, generator=None, byte_colour=False) -> SceneAugment:
     """Draw what read_scene (scannet.py:161-247) draws, with its probabilities and ranges, from ``generator`` (a
     numpy Generator; a fresh default_rng() if None).  Per-point noise (position jitter, colour jitter) and the noise grids
     are carried as seeds for the device generator, so ``n_points_hint`` is not needed for them and is accepted only for
@@ -77,13 +92,21 @@ def draw_params(cfg, n_points_hint=None, generator=None) -> SceneAugment:
       * mesh.transform(Rt) -> ('affine', Rt[:3,:3], 'origin', Rt[:3,3]).
     They are isolated here: augment_scenes and the kernels see explicit matrices and centres only.
 
-    cfg.apply_hue_aug, cfg.mix_3d_color_aug and cfg.random_brightness[0] > 0 raise NotImplementedError (albumentations)."""
-    for name in ('apply_hue_aug', 'mix_3d_color_aug'):
-        if getattr(cfg, name, False):
-            raise NotImplementedError('%s needs albumentations / cv2, which this package does not carry' % name)
+    cfg.apply_hue_aug, cfg.mix_3d_color_aug and cfg.random_brightness[0] > 0 raise NotImplementedError (albumentations)
+    unless ``byte_colour=True``: then they are drawn too, after the older colour steps and in the reference's order
+    (scannet.py:237-247), to be applied by the restated rule of profiles/colour8_rule.md.  With both mix_3d_color_aug and
+    apply_hue_aug the reference quantises already-normalised colours: ValueError."""
     rb = getattr(cfg, 'random_brightness', None)
-    if rb is not None and rb[0] > 0:
-        raise NotImplementedError('random_brightness needs albumentations / cv2, which this package does not carry')
+    if not byte_colour:
+        refusal = ('%s needs albumentations / cv2, which this package does not carry; draw_params(..., byte_colour=True) '
+                   'applies the restated rule of profiles/colour8_rule.md instead')
+        for name in ('apply_hue_aug', 'mix_3d_color_aug'):
+            if getattr(cfg, name, False):
+                raise NotImplementedError(refusal % name)
+        if rb is not None and rb[0] > 0:
+            raise NotImplementedError(refusal % 'random_brightness')
+    elif getattr(cfg, 'mix_3d_color_aug', False) and getattr(cfg, 'apply_hue_aug', False):
+        raise ValueError('mix_3d_color_aug and apply_hue_aug together quantise colours that are already normalised: set one')
     out = SceneAugment()
     if not getattr(cfg, 'augmentation', False):
         return out
@@ -130,7 +153,52 @@ def draw_params(cfg, n_points_hint=None, generator=None) -> SceneAugment:
     cj = getattr(cfg, 'color_jittering_aug', [0, .1])
     if rng.random() < cj[0]:                                                        # :234-235
         c.append(('jitter', -float(cj[1]), float(cj[1]), seed()))
+    if not byte_colour:
+        return out
+    if rb is not None and rng.random() < rb[0]:                                     # :237-239, augmentation.py:63-66
+        c.append(('brightness', float(rng.uniform(-rb[1], rb[1]))))
+    hue = getattr(cfg, 'apply_hue_aug', False)
+    if hue or getattr(cfg, 'mix_3d_color_aug', False):                              # :241-247
+        hsv = tuple(float(rng.uniform(-lim, lim)) for lim in HUE_LIMITS) if hue else ()
+        contrast, bright, shift = MIX3D_LIMITS          # always_apply: both Mix3D transforms run whatever their p
+        mix = (1.0 + float(rng.uniform(-contrast, contrast)), float(rng.uniform(-bright, bright)),
+               tuple(float(rng.uniform(-shift, shift)) for _ in range(3)))
+        c.append((('hue',) + hsv + mix) if hue else (('mix3d',) + mix))
     return out
+
+
+# ---- byte-colour tables (profiles/colour8_rule.md): the numpy statements of albumentations 1.0.3, one implementation for the
+# ---- device path; tests/_colour8_rule.py restates them
+
+def hsv_tables(hue_shift, sat_shift, val_shift):
+    """_shift_hsv_uint8's 256-entry tables (hue, sat, val), None for a zero shift; all three None skips the conversion."""
+    ramp = np.arange(0, 256, dtype=np.int16)
+    return (np.mod(ramp + float(hue_shift), 180).astype(np.uint8) if hue_shift != 0 else None,
+            np.clip(ramp + float(sat_shift), 0, 255).astype(np.uint8) if sat_shift != 0 else None,
+            np.clip(ramp + float(val_shift), 0, 255).astype(np.uint8) if val_shift != 0 else None)
+
+
+def rgb_tables(alpha, beta, shifts):
+    """RandomBrightnessContrast (brightness_by_max) then RGBShift on uint8, composed: three 256-entry tables (r, g, b)."""
+    lut = np.arange(0, 256).astype('float32')
+    if alpha != 1:
+        lut *= np.float32(alpha)
+    if beta != 0:
+        lut += np.float32(float(beta) * 255)
+    bc = np.clip(lut, 0, 255).astype(np.uint8)
+    out = []
+    for shift in shifts:
+        lut = np.arange(0, 256).astype('float32')
+        lut += np.float32(shift)
+        out.append(np.ascontiguousarray(np.clip(lut, 0, 255).astype(np.uint8)[bc]))
+    return tuple(out)
+
+
+def norm_rows(mean=COLOR_MEAN, std=COLOR_STD):
+    """A.Normalize's fp32 rows: (mean * 255, 1 / (std * 255))."""
+    m = np.array(mean, np.float32); m *= np.float32(255.0)
+    s = np.array(std, np.float32); s *= np.float32(255.0)
+    return m, np.reciprocal(s, dtype=np.float32)
 
 
 # ---- grid geometry on the host (what the reference computes with numpy; tests/test_augment.py holds it to the fixture)
@@ -251,17 +319,28 @@ def vertex_normals(pos, faces, csr):
 
 
 def colour_(colors, steps, generator_device=None):
-    """In place: the colour steps of a SceneAugment in one min/max reduction and one fused pass."""
+    """In place: the colour steps of a SceneAugment in one min/max reduction and one fused pass, and the byte-colour steps
+    ('brightness', 'mix3d' | 'hue'; profiles/colour8_rule.md) in one more pass after it."""
     flags, blend, tr, jit = 0, 0.0, None, None
+    bright, chain = None, None
     seen = []
     for s in steps:
-        if seen and ('auto_contrast', 'translation', 'jitter').index(s[0]) <= seen[-1]:
-            raise ValueError('colour steps must follow the reference order: auto_contrast, translation, jitter')
-        seen.append(('auto_contrast', 'translation', 'jitter').index(s[0]))
+        if s[0] not in _COLOUR_ORDER:
+            raise ValueError('unknown colour step %r' % (s[0],))
+        if seen and _COLOUR_ORDER.index(s[0]) <= seen[-1]:
+            raise ValueError('colour steps must follow the reference order: auto_contrast, translation, jitter'
+                             + (', brightness, mix3d, hue' if max(seen[-1], _COLOUR_ORDER.index(s[0])) > 2 else ''))
+        seen.append(_COLOUR_ORDER.index(s[0]))
         if s[0] == 'auto_contrast':
             flags |= 1; blend = float(s[1])
         elif s[0] == 'translation':
             flags |= 2; tr = _f64(s[1], 3)
+        elif s[0] == 'brightness':
+            bright = float(s[1])
+        elif s[0] in ('mix3d', 'hue'):
+            if chain is not None:
+                raise ValueError('mix3d and hue together quantise colours that are already normalised: use one')
+            chain = s
         else:
             flags |= 4
             lo, hi, src = s[1], s[2], s[3]
@@ -272,10 +351,20 @@ def colour_(colors, steps, generator_device=None):
                 jit = _dev(src, torch.float64, colors.device)
                 if jit.shape != colors.shape:
                     raise ValueError('colour jitter array must have the colours\' shape')
-    if not flags:
-        return colors
-    stats = column_stats(colors) if flags & 1 else None
-    _lib.call('b2m_aug_colour', ptr(colors), colors.shape[0], ptr(stats), flags, blend, _hp(tr) if tr is not None else None, ptr(jit))
+    if flags:
+        stats = column_stats(colors) if flags & 1 else None
+        _lib.call('b2m_aug_colour', ptr(colors), colors.shape[0], ptr(stats), flags, blend, _hp(tr) if tr is not None else None,
+                  ptr(jit))
+    if chain is not None:
+        # brightness leaves float32 colours, and numpy then forms colour * 255 in float32
+        hsv = hsv_tables(*chain[1:4]) if chain[0] == 'hue' else (None, None, None)
+        rgb = rgb_tables(*chain[-3:])
+        mean, den = norm_rows()
+        _lib.call('b2m_aug_colour8', ptr(colors), colors.shape[0], 3 if bright is not None else 0,
+                  bright if bright is not None else 0.0, *[_hp(t) if t is not None else None for t in hsv + rgb],
+                  _hp(mean), _hp(den))
+    elif bright is not None:
+        _lib.call('b2m_aug_brightness', ptr(colors), colors.shape[0], bright)
     return colors
 
 

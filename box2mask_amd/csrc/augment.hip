@@ -4,7 +4,7 @@
 //
 // Everything is a streaming pass over P x 24 bytes or over a noise grid that fits in L2: one thread per point / grid
 // element / vertex / instance, fp64 arithmetic without contraction (the reference is numpy fp64), no LDS beyond the
-// block reductions, no floating-point atomics (min / max go through order-preserving integer codes, sums through a
+// block reductions and the byte-colour tables, no floating-point atomics (min / max go through order-preserving integer codes, sums through a
 // fixed tree), so every result is the same bits run to run.
 #include "b2m_common.h"
 #include "../../include/b2m_prepare.h"
@@ -329,6 +329,150 @@ extern "C" int b2m_aug_colour(double* colors, int64_t n, const double* stats, in
     Vec3 tr = {{0, 0, 0}};
     if (tr_host) for (int k = 0; k < 3; ++k) tr.v[k] = tr_host[k];
     aug_colour_kernel<<<(unsigned)cdiv64(n * 3, AUG_THREADS), AUG_THREADS, 0, st>>>(colors, n * 3, stats, flags, blend, tr, jitter);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+
+// ------------------------------------------------------------------ byte colours: brightness, hue step, Mix3D tables, normalisation
+// random_brightness (augmentation.py:63-66), apply_mix3d_color_aug (:148-156) and apply_hue_aug (:158-168) as the exact rule of
+// profiles/colour8_rule.md (restated in tests/_colour8_rule.py): an optional float32 brightness stage, then quantise -> [RGB->HSV,
+// one table per shifted channel, HSV->RGB] -> one composed table per RGB channel -> (u8 - mean) * den in fp32.  The 8-bit
+// conversions are OpenCV's integer RGB->HSV (hue range 180) and its fp32 HSV->RGB.  One thread per point, one streaming pass; the
+// whole parameter block travels as a kernel argument and is spread to LDS by each block, so the step costs no copy and no host read.
+#define AUG_C8_F32_PRODUCT 1
+#define AUG_C8_BRIGHTNESS 2
+struct Colour8Args {
+    uint32_t tab[6 * 64];                   // 256-byte tables: hue, sat, val, then r, g, b
+    float mean[3], den[3];
+    float beta;
+    int32_t flags, hsv;                     // hsv: bit k = the table of HSV channel k is present; 0 = no conversion at all
+};
+
+// (color * 255).astype(uint8): truncation; NaN and negative products give 0, products above 255 give 255 (numpy leaves them undefined)
+__device__ __forceinline__ int aug_c8_quant(double c, bool f32) {
+    if (f32) {
+        const float p = (float)c * 255.0f;
+        return !(p > 0.0f) ? 0 : (p >= 255.0f ? 255 : (int)p);
+    }
+    const double p = c * 255.0;
+    return !(p > 0.0) ? 0 : (p >= 255.0 ? 255 : (int)p);
+}
+__device__ __forceinline__ int aug_c8_sat(float x) {              // saturate(rint(x * 255)), round half to even
+    const float r = rintf(x * 255.0f);
+    return !(r > 0.0f) ? 0 : (r >= 255.0f ? 255 : (int)r);
+}
+
+template <bool BYTES>
+__global__ __launch_bounds__(AUG_THREADS) void aug_colour8_kernel(double* __restrict__ col, int64_t n, Colour8Args a) {
+    __shared__ uint32_t tab_w[6 * 64];
+    __shared__ int32_t sdiv[256], hdiv[256];
+    const uint8_t* tab = (const uint8_t*)tab_w;
+    if (BYTES) {
+        for (int k = threadIdx.x; k < 6 * 64; k += AUG_THREADS) tab_w[k] = a.tab[k];
+        if (a.hsv) {
+            for (int i = threadIdx.x; i < 256; i += AUG_THREADS) {
+                sdiv[i] = i ? (int32_t)rint((double)(255 << 12) / (1.0 * (double)i)) : 0;
+                hdiv[i] = i ? (int32_t)rint((double)(180 << 12) / (6.0 * (double)i)) : 0;
+            }
+        }
+        __syncthreads();
+    }
+    for (int64_t p = (int64_t)blockIdx.x * AUG_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * AUG_THREADS) {
+        double c[3] = {col[3 * p], col[3 * p + 1], col[3 * p + 2]};
+        if (a.flags & AUG_C8_BRIGHTNESS) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float v = (float)c[k];
+                v = v + a.beta;
+                v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);                  // NaN stays NaN (np.clip)
+                c[k] = (double)v;
+            }
+        }
+        if (BYTES) {
+            const bool f32 = (a.flags & AUG_C8_F32_PRODUCT) != 0;
+            int r = aug_c8_quant(c[0], f32), g = aug_c8_quant(c[1], f32), b = aug_c8_quant(c[2], f32);
+            if (a.hsv) {
+                // RGB -> HSV, integers; the order of the tests is the tie rule
+                const int v = max(r, max(g, b)), d = v - min(r, min(g, b));
+                int s = (d * sdiv[v] + 2048) >> 12;
+                int h = v == r ? g - b : (v == g ? b - r + 2 * d : r - g + 4 * d);
+                h = (h * hdiv[d] + 2048) >> 12;
+                if (h < 0) h += 180;
+                int H = h, S = s, V = v;
+                if (a.hsv & 1) H = tab[H & 255];
+                if (a.hsv & 2) S = tab[256 + (S & 255)];
+                if (a.hsv & 4) V = tab[512 + V];
+                // HSV -> RGB, fp32
+                float hf = (float)H * (6.0f / 180.0f);
+                const float sf = (float)S * (1.0f / 255.0f), vf = (float)V * (1.0f / 255.0f);
+                float fb = vf, fg = vf, fr = vf;
+                if (sf != 0.0f) {
+                    hf = fmodf(hf, 6.0f);
+                    int sector = (int)floorf(hf);
+                    hf = hf - (float)sector;
+                    if (sector < 0 || sector > 5) { sector = 0; hf = 0.0f; }
+                    const float t1 = vf * (1.0f - sf), t2 = vf * (1.0f - sf * hf), t3 = vf * (1.0f - sf * (1.0f - hf));
+                    // (b, g, r) = tab[T[sector]], T = {{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}} over tab = {v, t1, t2, t3}
+                    switch (sector) {
+                        case 0: fb = t1; fg = t3; fr = vf; break;
+                        case 1: fb = t1; fg = vf; fr = t2; break;
+                        case 2: fb = t3; fg = vf; fr = t1; break;
+                        case 3: fb = vf; fg = t2; fr = t1; break;
+                        case 4: fb = vf; fg = t1; fr = t3; break;
+                        default: fb = t2; fg = t1; fr = vf; break;
+                    }
+                }
+                r = aug_c8_sat(fr); g = aug_c8_sat(fg); b = aug_c8_sat(fb);
+            }
+            r = tab[768 + r]; g = tab[1024 + g]; b = tab[1280 + b];
+            c[0] = (double)(((float)r - a.mean[0]) * a.den[0]);
+            c[1] = (double)(((float)g - a.mean[1]) * a.den[1]);
+            c[2] = (double)(((float)b - a.mean[2]) * a.den[2]);
+        }
+        col[3 * p] = c[0]; col[3 * p + 1] = c[1]; col[3 * p + 2] = c[2];
+    }
+}
+
+static unsigned aug_colour8_blocks(int64_t n) {
+    const int64_t nb = cdiv64(n, AUG_THREADS);
+    return (unsigned)(nb > 2048 ? 2048 : nb);                 // 8 blocks on each of the 256 CUs, then a grid-stride loop
+}
+
+extern "C" int b2m_aug_colour8(double* colors, int64_t n, int32_t flags, float beta, const uint8_t* hue_tab_host,
+                               const uint8_t* sat_tab_host, const uint8_t* val_tab_host, const uint8_t* r_tab_host,
+                               const uint8_t* g_tab_host, const uint8_t* b_tab_host, const float* mean_host, const float* den_host,
+                               void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(colors, "NULL pointer");
+    B2M_CHECK_ARG(n > 0, "n must be positive");
+    B2M_CHECK_ARG(flags >= 0 && flags < 4, "unknown flags");
+    B2M_CHECK_ARG(r_tab_host && g_tab_host && b_tab_host, "the three RGB tables are needed");
+    B2M_CHECK_ARG(mean_host && den_host, "the normalisation needs its mean and reciprocal rows");
+    Colour8Args a = {};
+    const uint8_t* tabs[6] = {hue_tab_host, sat_tab_host, val_tab_host, r_tab_host, g_tab_host, b_tab_host};
+    uint8_t* bytes = (uint8_t*)a.tab;
+    for (int k = 0; k < 6; ++k) {
+        if (!tabs[k]) continue;
+        for (int i = 0; i < 256; ++i) bytes[256 * k + i] = tabs[k][i];
+        if (k < 3) a.hsv |= 1 << k;
+    }
+    for (int k = 0; k < 3; ++k) { a.mean[k] = mean_host[k]; a.den[k] = den_host[k]; }
+    a.beta = beta;
+    a.flags = flags;
+    aug_colour8_kernel<true><<<aug_colour8_blocks(n), AUG_THREADS, 0, st>>>(colors, n, a);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+
+// random_brightness alone: colors <- clip(float32(colors) + beta, 0, 1), the float32 values widened back to fp64
+extern "C" int b2m_aug_brightness(double* colors, int64_t n, float beta, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(colors, "NULL pointer");
+    B2M_CHECK_ARG(n > 0, "n must be positive");
+    Colour8Args a = {};
+    a.beta = beta;
+    a.flags = AUG_C8_BRIGHTNESS;
+    aug_colour8_kernel<false><<<aug_colour8_blocks(n), AUG_THREADS, 0, st>>>(colors, n, a);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }

@@ -153,6 +153,23 @@ int b2m_aug_vertex_normals(const double* pos, int64_t n_vert, const int64_t* fac
 int b2m_aug_colour(double* colors, int64_t n, const double* stats, int32_t flags, double blend, const double* tr_host,
                    const double* jitter, void* stream);
 
+/* The byte-colour chain of apply_mix3d_color_aug / apply_hue_aug (augmentation.py:148-168) in one pass over the (n,3) colours,
+ * by the exact rule of profiles/colour8_rule.md: [flags & 2: colors <- clip(float32(colors) + beta, 0, 1), random_brightness
+ * (:63-66)] -> u8 = trunc(colors * 255) (flags & 1: the product in fp32, as numpy forms it once random_brightness has made the
+ * colours float32; else fp64; NaN and negative give 0, above 255 gives 255) -> [RGB->HSV in 8 bits (hue range 180), the HSV
+ * tables, HSV->RGB in 8 bits] -> the RGB tables -> (float32(u8) - mean) * den in fp32, widened to fp64.  Every table is 256
+ * bytes on the host.  Each of hue / sat / val_tab_host may be NULL (albumentations skips the table of a zero shift); all three
+ * NULL means no colour-space conversion at all (the Mix3D chain).  r / g / b_tab_host are RandomBrightnessContrast and RGBShift
+ * composed; mean_host and den_host are 3 floats each: mean * 255 and 1 / (std * 255).  No host read, no copy, no atomics. */
+int b2m_aug_colour8(double* colors, int64_t n, int32_t flags, float beta, const uint8_t* hue_tab_host,
+                    const uint8_t* sat_tab_host, const uint8_t* val_tab_host, const uint8_t* r_tab_host,
+                    const uint8_t* g_tab_host, const uint8_t* b_tab_host, const float* mean_host, const float* den_host,
+                    void* stream);
+
+/* random_brightness alone (augmentation.py:63-66 with contrast 0): colors <- clip(float32(colors) + beta, 0, 1), NaN kept,
+ * the float32 values widened back to fp64. */
+int b2m_aug_brightness(double* colors, int64_t n, float beta, void* stream);
+
 /* compute_bounding_box (scannet.py:321-367) for instance ids in [0, n_inst): per-instance fp64 min / max by 64-bit integer
  * atomics (order independent), semantics of the lowest-index point, centre = (min + max) / 2, bounds = max - centre, cast to
  * float32 where the reference stores them; a second pass for offsets = centre - point, their norms and the radius.

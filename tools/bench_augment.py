@@ -98,6 +98,13 @@ def np_vertex_normals(pos, faces):
     return acc / np.maximum(np.linalg.norm(acc, axis=1, keepdims=True), 1e-300)
 
 
+def np_hue(col, steps):
+    """The numpy statement of the byte-colour chain (the rule the device pass is held to, tests/_colour8_rule.py)."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import _colour8_rule
+    return _colour8_rule.colour_steps(col, steps)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--points', type=int, default=150000)
@@ -150,6 +157,33 @@ def main(argv=None):
         return np.clip(jit_h + c, 0, 1)
     rows.append(['colour: min/max + fused contrast / translation / jitter', timed(lambda: augment.colour_(work, steps), args.repeats),
                  None if args.no_cpu else host(np_colour)])
+    hue = [('brightness', 0.1), ('hue', 10.7, -12.5, 7.25, 1.1, -0.1, (5.5, -20.0, 3.3))]
+    work8 = col.clone()
+
+    def fresh_hue():                         # the chain leaves normalised colours: every repeat starts from colours in [0, 1]
+        work8.copy_(col)
+        augment.colour_(work8, hue)
+    t_copy = timed(lambda: work8.copy_(col), args.repeats)
+    rows.append(['byte colours through colour_: the host builds the tables, then brightness + hue step + Mix3D tables + normalise in one '
+                 'pass (less the %.3f ms refill of its input; the device waits for the host here)' % t_copy,
+                 timed(fresh_hue, args.repeats) - t_copy, None if args.no_cpu else host(lambda: np_hue(col_h, hue))])
+    # the pass alone: prebuilt tables, 16 launches back to back on 16 fresh copies of the colours
+    tabs = list(augment.hsv_tables(*hue[1][1:4])) + list(augment.rgb_tables(*hue[1][4:]))
+    rows8 = augment.norm_rows()
+    hp = [augment._hp(t) for t in tabs + list(rows8)]
+    copies = [col.clone() for _ in range(16)]
+
+    def refill():
+        for c in copies:
+            c.copy_(col)
+
+    def passes():
+        refill()
+        for c in copies:
+            augment._lib.call('b2m_aug_colour8', c.data_ptr(), P, 3, 0.1, *hp)
+    t_refill = timed(refill, args.repeats)
+    rows.append(['byte colours, b2m_aug_colour8 alone with prebuilt tables (16 launches back to back, per launch)',
+                 (timed(passes, args.repeats) - t_refill) / 16, None])
     scene = {'positions': pos}
     t0 = timed(lambda: augment.instance_labels(scene, sem, inst, None), args.repeats)
     rows.append(['instance boxes, %d instances (whole instance_labels, two host reads)' % (int(inst_h.max()) + 1), t0,

@@ -4,11 +4,14 @@ batch (prepare.voxelize_scene / box_supervision / collate) -> training steps as 
 instances (eval_metric.compute_eval).  With --metric arkit the furniture instances are scored as oriented boxes as well
 (their labels' boxes, a yaw of zero): the ARKitScenes detection mAP of eval_detection.arkitscenes_eval after the last step.
 
-    python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 [--half 1] [--metric arkit] [--augment]
+    python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 [--half 1] [--metric arkit] [--augment [--hue]]
 
 --augment (off by default): every step trains on a batch whose scenes went through augment.augment_scenes with parameters drawn per
 scene per step from the values of configs/scannet.txt (rotation_90_aug, flipping_aug 0.5, scaling_aug 0.8 - 1.2) and whose box
 labels augment.instance_labels recomputed from the augmented positions; the evaluations stay on the un-augmented scenes.
+--hue (with --augment): apply_hue_aug of configs/scannet.txt:37 as well, drawn with draw_params(..., byte_colour=True) and applied by
+the byte-colour rule of profiles/colour8_rule.md, which also normalises the colours.  The evaluation colours are then UN-normalised --
+as in the reference, whose evaluation skips the whole augmentation block (do_augmentations=False, scannet.py:221-247).
 """
 import argparse
 import os
@@ -41,9 +44,9 @@ def build_batch(seeds, voxels, mode, cfg_sup):
     return prepare.collate(items, mode), raws
 
 
-def augmented_batch(raws, aug_cfg, rng, cfg_sup):
+def augmented_batch(raws, aug_cfg, rng, cfg_sup, byte_colour=False):
     """One training batch of freshly augmented scenes: parameters per scene, labels from the augmented positions."""
-    outs = augment.augment_scenes(raws, [augment.draw_params(aug_cfg, generator=rng) for _ in raws])
+    outs = augment.augment_scenes(raws, [augment.draw_params(aug_cfg, generator=rng, byte_colour=byte_colour) for _ in raws])
     items = prepare.voxelize_scenes(outs, 0.02)
     for it, out, raw in zip(items, outs, raws):
         lab = raw['labels']
@@ -107,9 +110,13 @@ def main(argv=None):
                     help='arkit: the oriented-box detection mAP (eval_detection.py) beside the ScanNet AP')
     ap.add_argument('--augment', action='store_true',
                     help='train on scenes augmented on the device, parameters drawn per scene per step (augment.py)')
+    ap.add_argument('--hue', action='store_true',
+                    help='with --augment: apply_hue_aug too, by the byte-colour rule (training colours come out normalised)')
     ap.add_argument('--checkpoint-dir', default=None,
                     help='keep the checkpoint here (tools/param_search.py reads it); default: a temporary directory')
     args = ap.parse_args(argv)
+    if args.hue and not args.augment:
+        ap.error('--hue needs --augment')
     torch.manual_seed(args.seed)
     cfg = scannet_config(lr=args.lr, mlp_bb_scores_start_epoch=0, half_training=bool(args.half),       # score head trained from the first step
                          half_loss_scale='dynamic' if args.loss_scale == 'dynamic' else float(args.loss_scale))
@@ -119,7 +126,8 @@ def main(argv=None):
     sup = SimpleNamespace(smallest_bb_heuristic=True)
     batch, raws = build_batch(range(args.scenes), args.voxels, 'train', sup)
     if args.augment:
-        aug_cfg = scannet_config(augmentation=True, rotation_90_aug=True, flipping_aug=0.5, scaling_aug=[1.0, 0.8, 1.2])   # configs/scannet.txt:32-36
+        aug_cfg = scannet_config(augmentation=True, rotation_90_aug=True, flipping_aug=0.5, scaling_aug=[1.0, 0.8, 1.2],   # configs/scannet.txt:32-36
+                                 apply_hue_aug=args.hue)                                                                    # :37
         aug_rng = np.random.default_rng(args.seed)
     model = Model(cfg, *synth.scannet_tables())
     opt = torch.optim.Adam(model.parameters(), lr=cfg.lr, fused=True)
@@ -129,7 +137,7 @@ def main(argv=None):
     t0 = time.time()
     for step in range(args.steps):
         opt.zero_grad()
-        losses = model.compute_loss(augmented_batch(raws, aug_cfg, aug_rng, sup) if args.augment else batch, epoch=step)
+        losses = model.compute_loss(augmented_batch(raws, aug_cfg, aug_rng, sup, args.hue) if args.augment else batch, epoch=step)
         losses['optimization_loss'].backward()
         opt.step()
         if step % 10 == 0 or step == args.steps - 1:
