@@ -100,6 +100,8 @@ PROTOTYPES = {
     'b2m_mask_pack': [P, I32, I64, P, I64, P],
     'b2m_set_ious': [P, P, I64, P, P],
     'b2m_mask_hulls': [P, I64, I32, P, I64, P, P, P, I32, P, P, P, P, P, P, P],
+    'b2m_mask_hulls_index': [P, I64, I32, I64, P, P, I64, P, P, P, P, I32, P, P, P, P, P, P, P],
+    'b2m_mask_hulls_index_batch': [P, I32, I32, I32, I64, P],
     'b2m_obb_corners': [P, P, P, I32, P, P],
     'b2m_hull_box_iou': [P, P, P, P, I32, P, P, I32, P, P],
     'b2m_aabb_iou': [P, P, I32, P, P, P, I32, P, P],

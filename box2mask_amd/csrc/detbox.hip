@@ -47,9 +47,9 @@ __device__ __forceinline__ void scan_bits(const uint64_t* __restrict__ row, int6
 }
 
 // ---- pass 1: count, axis-aligned box and the extreme point along each direction, per (row, chunk of words)
-__global__ __launch_bounds__(256) void hull_extreme_kernel(const uint64_t* __restrict__ bits, int64_t words, const double* __restrict__ pos,
-                                                           int64_t n, int64_t wpb, int nchunk, double* __restrict__ part) {
-    const int r = blockIdx.y, chunk = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6;
+__device__ __forceinline__ void hull_extreme(const uint64_t* __restrict__ bits, int64_t words, const double* __restrict__ pos, int64_t n,
+                                             int64_t wpb, int nchunk, double* __restrict__ part, int r, int chunk) {
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int64_t w0 = (int64_t)chunk * wpb;
     int64_t w1 = w0 + wpb;
     if (w1 > words) w1 = words;
@@ -118,10 +118,10 @@ __global__ __launch_bounds__(256) void hull_extreme_kernel(const uint64_t* __res
 }
 
 // ---- pass 2: keep the points that are not strictly inside the polygon of the row's extremes (the only hull candidates)
-__global__ __launch_bounds__(256) void hull_filter_kernel(const uint64_t* __restrict__ bits, int64_t words, const double* __restrict__ pos,
-                                                          int64_t n, int64_t wpb, int nchunk, const double* __restrict__ part,
-                                                          double* __restrict__ cand, int32_t cap, int32_t* __restrict__ ncand) {
-    const int r = blockIdx.y, chunk = blockIdx.x, lane = lane_id();
+__device__ __forceinline__ void hull_filter(const uint64_t* __restrict__ bits, int64_t words, const double* __restrict__ pos, int64_t n,
+                                            int64_t wpb, int nchunk, const double* __restrict__ part, double* __restrict__ cand,
+                                            int32_t cap, int32_t* __restrict__ ncand, int r, int chunk) {
+    const int lane = lane_id();
     const int64_t w0 = (int64_t)chunk * wpb;
     int64_t w1 = w0 + wpb;
     if (w1 > words) w1 = words;
@@ -178,12 +178,11 @@ __global__ __launch_bounds__(256) void hull_filter_kernel(const uint64_t* __rest
 __device__ __forceinline__ bool lex_less(double ax, double ay, double bx, double by) { return ax < bx || (ax == bx && ay < by); }
 
 // ---- pass 3: exact hull of the candidates of one row (Andrew's monotone chain over the lexicographically sorted candidates)
-__global__ __launch_bounds__(256) void hull_exact_kernel(const double* __restrict__ part, int nchunk, double* __restrict__ cand, int32_t cap,
-                                                         const int32_t* __restrict__ ncand, int32_t* __restrict__ stk,
-                                                         int32_t* __restrict__ count, double* __restrict__ box6,
-                                                         double* __restrict__ hull, int32_t* __restrict__ n_hull,
-                                                         int32_t* __restrict__ flags) {
-    const int r = blockIdx.x, t = threadIdx.x;
+__device__ __forceinline__ void hull_exact(const double* __restrict__ part, int nchunk, double* __restrict__ cand, int32_t cap,
+                                           const int32_t* __restrict__ ncand, int32_t* __restrict__ stk, int32_t* __restrict__ count,
+                                           double* __restrict__ box6, double* __restrict__ hull, int32_t* __restrict__ n_hull,
+                                           int32_t* __restrict__ flags, int r) {
+    const int t = threadIdx.x;
     __shared__ double s_a[LCAP * 2];
     __shared__ int s_stk[LCAP];
     __shared__ int s_h;
@@ -265,6 +264,33 @@ __global__ __launch_bounds__(256) void hull_exact_kernel(const double* __restric
     }
 }
 
+__global__ __launch_bounds__(256) void hull_extreme_kernel(const uint64_t* __restrict__ bits, int64_t words, const double* __restrict__ pos,
+                                                           int64_t n, int64_t wpb, int nchunk, double* __restrict__ part) {
+    hull_extreme(bits, words, pos, n, wpb, nchunk, part, blockIdx.y, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void hull_filter_kernel(const uint64_t* __restrict__ bits, int64_t words, const double* __restrict__ pos,
+                                                          int64_t n, int64_t wpb, int nchunk, const double* __restrict__ part,
+                                                          double* __restrict__ cand, int32_t cap, int32_t* __restrict__ ncand) {
+    hull_filter(bits, words, pos, n, wpb, nchunk, part, cand, cap, ncand, blockIdx.y, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void hull_exact_kernel(const double* __restrict__ part, int nchunk, double* __restrict__ cand, int32_t cap,
+                                                         const int32_t* __restrict__ ncand, int32_t* __restrict__ stk,
+                                                         int32_t* __restrict__ count, double* __restrict__ box6,
+                                                         double* __restrict__ hull, int32_t* __restrict__ n_hull,
+                                                         int32_t* __restrict__ flags) {
+    hull_exact(part, nchunk, cand, cap, ncand, stk, count, box6, hull, n_hull, flags, blockIdx.x);
+}
+
+// at most CHUNKS blocks per row, each at least 1024 words (whole groups of 64)
+__host__ __device__ __forceinline__ int64_t hull_wpb(int64_t words) {
+    const int64_t wpb = (((words + CHUNKS - 1) / CHUNKS + 63) / 64) * 64;
+    return wpb < 1024 ? 1024 : wpb;
+}
+__host__ __device__ __forceinline__ int hull_nchunk(int64_t words) {
+    const int64_t wpb = hull_wpb(words);
+    return words == 0 ? 1 : (int)((words + wpb - 1) / wpb);
+}
+
 extern "C" int b2m_mask_hulls(const uint64_t* bits, int64_t words, int32_t k, const double* pos, int64_t n, double* work, double* cand,
                               int32_t* stk, int32_t cap, int32_t* ncand, int32_t* count, double* box6, double* hull, int32_t* n_hull,
                               int32_t* flags, void* stream) {
@@ -275,14 +301,118 @@ extern "C" int b2m_mask_hulls(const uint64_t* bits, int64_t words, int32_t k, co
     if (k == 0) return B2M_OK;
     B2M_CHECK_ARG(bits && work && cand && stk && ncand && count && box6 && hull && n_hull && flags, "NULL argument");
     B2M_CHECK_ARG(pos || n == 0, "NULL positions");
-    // at most CHUNKS blocks per row, each at least 1024 words (whole groups of 64)
-    int64_t wpb = cdiv64(cdiv64(words, CHUNKS), 64) * 64;
-    if (wpb < 1024) wpb = 1024;
-    const int nchunk = words == 0 ? 1 : (int)cdiv64(words, wpb);
+    const int64_t wpb = hull_wpb(words);
+    const int nchunk = hull_nchunk(words);
     B2M_HIP(hipMemsetAsync(ncand, 0, (size_t)k * sizeof(int32_t), st));
     hull_extreme_kernel<<<dim3((unsigned)nchunk, (unsigned)k), 256, 0, st>>>(bits, words, pos, n, wpb, nchunk, work);
     hull_filter_kernel<<<dim3((unsigned)nchunk, (unsigned)k), 256, 0, st>>>(bits, words, pos, n, wpb, nchunk, work, cand, cap, ncand);
     hull_exact_kernel<<<dim3((unsigned)k), 256, 0, st>>>(work, nchunk, cand, cap, ncand, stk, count, box6, hull, n_hull, flags);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+
+// ------------------------------------------------------------------ hulls of masks that live on voxels, asked about on points
+// b2m_mask_gather -> b2m_mask_pack -> b2m_mask_hulls without the k x n_pts bytes.  The rows are expanded to POINT bit rows first
+// (one bit per point and row: k x n_pts / 8 bytes of scratch) and the three passes above run over those, so point indices, ties,
+// chunks and candidates are those of the definition.  Why not a gathering bit source in scan_bits: the passes skip zero words
+// 64 at a time and read the 64 points of a set word as one contiguous piece; through the index every one of the three passes would
+// walk all n_pts of every row (a row holds a fraction of a percent of the scene) and gather a voxel word per point, three times.
+// Here a wave reads the index of its 64 points ONCE for XROWS rows and gathers from voxel rows of a few KB that stay in L2; the
+// ballot of the 64 lanes is the point word.
+struct HullScene {
+    const uint64_t* bits; int64_t k; int64_t words; int64_t n_vox; const int64_t* index; const double* pos; int64_t n_pts;
+    uint64_t* pbits; double* work; double* cand; int32_t* stk; int32_t* ncand; int32_t* count; double* box6; double* hull;
+    int32_t* n_hull; int32_t* flags;
+};
+static_assert(sizeof(HullScene) == B2M_HULLIDX_DESC * 8, "HullScene must match B2M_HULLIDX_DESC");
+#define XROWS 16                     // rows per block of the expansion
+// block (bx, by) of a scene: point words 4 bx .. 4 bx + 3 of rows XROWS by .. ; the blocks of bx = 0 zero ncand of their rows
+__device__ __forceinline__ void hull_expand(const HullScene& d, int64_t bx, int by) {
+    const int lane = lane_id();
+    const int64_t r0 = (int64_t)by * XROWS;
+    const int64_t r1 = r0 + XROWS < d.k ? r0 + XROWS : d.k;
+    if (bx == 0 && r0 + threadIdx.x < r1) d.ncand[r0 + threadIdx.x] = 0;
+    const int64_t pw = (d.n_pts + 63) >> 6;
+    const int64_t w = bx * 4 + (threadIdx.x >> 6);
+    if (w >= pw) return;                                                    // (whole waves)
+    const int64_t p = w * 64 + lane;
+    int64_t v = -1;
+    if (p < d.n_pts) v = d.index ? d.index[p] : p;
+    const bool ok = v >= 0 && v < d.n_vox;                                  // (a point that names no voxel lies in no mask)
+    const int64_t vw = ok ? v >> 6 : 0;
+    const int sh = (int)(v & 63);
+    for (int64_t r = r0; r < r1; ++r) {
+        const bool bit = ok && ((d.bits[r * d.words + vw] >> sh) & 1ull);
+        const uint64_t m = __ballot(bit);
+        if (lane == 0) d.pbits[r * pw + w] = m;
+    }
+}
+__global__ __launch_bounds__(256) void hull_expand_kernel(HullScene d) { hull_expand(d, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(256) void hull_expand_batch_kernel(const HullScene* __restrict__ sc) {
+    const HullScene d = sc[blockIdx.z];
+    if ((int64_t)blockIdx.y * XROWS >= d.k) return;
+    hull_expand(d, blockIdx.x, blockIdx.y);
+}
+__global__ __launch_bounds__(256) void hull_extreme_batch_kernel(const HullScene* __restrict__ sc) {
+    const HullScene d = sc[blockIdx.z];
+    const int64_t pw = (d.n_pts + 63) >> 6;
+    const int nchunk = hull_nchunk(pw);
+    if (blockIdx.y >= d.k || (int)blockIdx.x >= nchunk) return;
+    hull_extreme(d.pbits, pw, d.pos, d.n_pts, hull_wpb(pw), nchunk, d.work, blockIdx.y, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void hull_filter_batch_kernel(const HullScene* __restrict__ sc, int32_t cap) {
+    const HullScene d = sc[blockIdx.z];
+    const int64_t pw = (d.n_pts + 63) >> 6;
+    const int nchunk = hull_nchunk(pw);
+    if (blockIdx.y >= d.k || (int)blockIdx.x >= nchunk) return;
+    hull_filter(d.pbits, pw, d.pos, d.n_pts, hull_wpb(pw), nchunk, d.work, d.cand, cap, d.ncand, blockIdx.y, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void hull_exact_batch_kernel(const HullScene* __restrict__ sc, int32_t cap) {
+    const HullScene d = sc[blockIdx.y];
+    if (blockIdx.x >= d.k) return;
+    hull_exact(d.work, hull_nchunk((d.n_pts + 63) >> 6), d.cand, cap, d.ncand, d.stk, d.count, d.box6, d.hull, d.n_hull, d.flags,
+               blockIdx.x);
+}
+extern "C" int b2m_mask_hulls_index(const uint64_t* bits, int64_t words, int32_t k, int64_t n_vox, const int64_t* index, const double* pos,
+                                    int64_t n_pts, uint64_t* pbits, double* work, double* cand, int32_t* stk, int32_t cap, int32_t* ncand,
+                                    int32_t* count, double* box6, double* hull, int32_t* n_hull, int32_t* flags, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(k >= 0 && k <= 65535 && n_pts >= 0 && n_pts < 0x7fffffffll, "bad sizes (k <= 65535, n_pts < 2^31)");
+    B2M_CHECK_ARG(n_vox >= 0 && words == cdiv64(n_vox, 64), "bad sizes (words = ceil(n_vox / 64))");
+    B2M_CHECK_ARG(cap >= 64 && cap <= (1 << 24) && (cap & (cap - 1)) == 0, "cap: a power of two in [64, 2^24]");
+    if (k == 0) return B2M_OK;
+    B2M_CHECK_ARG(work && cand && stk && ncand && count && box6 && hull && n_hull && flags, "NULL argument");
+    B2M_CHECK_ARG((bits || words == 0) && ((pos && pbits) || n_pts == 0), "NULL argument");
+    const HullScene d{bits, k, words, n_vox, index, pos, n_pts, pbits, work, cand, stk, ncand, count, box6, hull, n_hull, flags};
+    const int64_t pw = cdiv64(n_pts, 64);
+    const int64_t wpb = hull_wpb(pw);
+    const int nchunk = hull_nchunk(pw);
+    const int64_t xb = pw == 0 ? 1 : cdiv64(pw, 4);
+    hull_expand_kernel<<<dim3((unsigned)xb, (unsigned)cdiv64(k, XROWS)), 256, 0, st>>>(d);
+    hull_extreme_kernel<<<dim3((unsigned)nchunk, (unsigned)k), 256, 0, st>>>(pbits, pw, pos, n_pts, wpb, nchunk, work);
+    hull_filter_kernel<<<dim3((unsigned)nchunk, (unsigned)k), 256, 0, st>>>(pbits, pw, pos, n_pts, wpb, nchunk, work, cand, cap, ncand);
+    hull_exact_kernel<<<dim3((unsigned)k), 256, 0, st>>>(work, nchunk, cand, cap, ncand, stk, count, box6, hull, n_hull, flags);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+extern "C" int b2m_mask_hulls_index_batch(const int64_t* desc, int32_t n_scenes, int32_t cap, int32_t max_k, int64_t max_pts,
+                                          void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(n_scenes >= 0 && n_scenes <= 65535 && max_k >= 0 && max_k <= 65535 && max_pts >= 0 && max_pts < 0x7fffffffll,
+                  "bad sizes (n_scenes, max_k <= 65535, max_pts < 2^31)");
+    B2M_CHECK_ARG(cap >= 64 && cap <= (1 << 24) && (cap & (cap - 1)) == 0, "cap: a power of two in [64, 2^24]");
+    if (n_scenes == 0 || max_k == 0) return B2M_OK;
+    B2M_CHECK_ARG(desc, "NULL argument");
+    const HullScene* sc = (const HullScene*)desc;
+    const int64_t pw = cdiv64(max_pts, 64);
+    // the chunks of a scene are not monotone in its size (32 of 1024 words, then 31 of 1088): a bound for every size up to pw
+    int nchunk = pw == 0 ? 1 : (int)cdiv64(pw, 1024);
+    if (nchunk > CHUNKS) nchunk = CHUNKS;
+    const int64_t xb = pw == 0 ? 1 : cdiv64(pw, 4);
+    hull_expand_batch_kernel<<<dim3((unsigned)xb, (unsigned)cdiv64(max_k, XROWS), (unsigned)n_scenes), 256, 0, st>>>(sc);
+    hull_extreme_batch_kernel<<<dim3((unsigned)nchunk, (unsigned)max_k, (unsigned)n_scenes), 256, 0, st>>>(sc);
+    hull_filter_batch_kernel<<<dim3((unsigned)nchunk, (unsigned)max_k, (unsigned)n_scenes), 256, 0, st>>>(sc, cap);
+    hull_exact_batch_kernel<<<dim3((unsigned)max_k, (unsigned)n_scenes), 256, 0, st>>>(sc, cap);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }

@@ -460,6 +460,12 @@ class SelectionNet(ResNetBase):
         from . import param_search
         return param_search.sweep_tables(self, batch, pred, cfg, grid, gt_ids, acc=acc)
 
+    def detection2mask_detection_sweep(self, batch, pred, cfg, grid, positions=None, labels=None, **kw):
+        """The same grid scored with the oriented-box detection mAP of ARKitScenes: one ``param_search.DetectionTables`` per scene,
+        from which ``param_search.detection_records`` reads the ``eval_detection.eval_det`` record of any setting."""
+        from . import param_search
+        return param_search.detection_tables(self, batch, pred, cfg, grid, positions, labels, **kw)
+
     # ------------------------------------------------------------------ prediction
     def get_prediction(self, batch, with_grad=True, to_cpu=False, to_numpy=False, min_size=True, sin=None):
         """detection_net.py:493-517.  `sin`: the batch's sparse tensor if the caller holds it already (Model.prefetch built it

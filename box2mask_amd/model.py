@@ -321,6 +321,10 @@ class Model:
         ``eval_match.MatchAccumulator``) the stage results stay on the device and are matched there."""
         return self.detection_model.detection2mask_sweep(batch, pred, self.cfg, grid, gt_ids, acc=acc)
 
+    def pred2mask_detection_sweep(self, batch, pred, grid, positions=None, labels=None, **kw):
+        """The tables of a whole threshold grid for the ARKitScenes detection mAP (param_search.detection_tables)."""
+        return self.detection_model.detection2mask_detection_sweep(batch, pred, self.cfg, grid, positions, labels, **kw)
+
     def parameters(self):
         return self.detection_model.parameters()
 

@@ -19,8 +19,20 @@ by default) and runs every setting as a CPU evaluation job of its own over the w
                                                                                      -> ``b2m_mask_hist_index``, no per-point mask.
 
 So 600 settings cost 6 clusterings and 24 mask stages per batch, a few host reads per stage, and the host matching of
-``eval_metric`` per setting.  ScanNet flow only (segment-level votes, mask NMS, the AP of eval_metric.py): that is what the
-reference's search scores.  ``compose`` and the matching are host logic like ``assign_from_counts``; every kernel stage is HIP.
+``eval_metric`` per setting.  Segment-level flow only (segment-level votes, mask NMS): a network with a per-voxel semantics head
+has no mask NMS to sweep.
+
+The reference's search is not ScanNet-specific: with ``dataset_name = arkitscenes`` every job ends in ``arkitscenes_eval``
+(evaluation.py:245-316), the oriented-box detection mAP.  The front half above is shared (``_cluster_stages``); what a stage is
+scored with differs:
+
+  * per projected row its point count, z range and x-y convex hull, and the IoU of that prism with every same-class ground-truth
+    box, depend on (cluster_th, mask_bin_th) alone -- score_th and mask_nms_th only select rows
+                                                                                     -> ``b2m_mask_hulls_index_batch`` + one IoU call per
+                                                                                        scene and stage: 24 hull stages, not 600;
+  * rows under 50 points are skipped AFTER the mask NMS (evaluation.py:280)          -> ``detection_records`` gates what ``compose`` kept.
+
+``detection_tables`` / ``detection_records`` / ``arkit_param_search``; matching and VOC AP are the unchanged ``eval_detection.eval_det``.  ``compose`` and the matching are host logic like ``assign_from_counts``; every kernel stage is HIP.
 With ``matching='device'`` the matching, the curves and the AP run on the device as well (eval_match.py): the stage results are
 matched where they lie and nothing but an entry count per stage comes to the host.
 """
@@ -33,6 +45,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import eval_detection
 from . import eval_metric
 from . import iou_nms
 from .util import to_bbs_min_max
@@ -187,60 +200,303 @@ def sweep_tables(net, batch, pred, cfg, grid, gt_ids, acc=None):
         d['G'] = max(len(uniq), 1)
         d['dense32'] = torch.from_numpy(dense.reshape(-1).astype(np.int32)).to(dev)
         tabs.append(SweepTables(d['name'], d['n_pts'], uniq.astype(np.int64), vert.astype(np.int64)))
+    for c in _cluster_stages(sc, grid, dev, tabs, n_class, _hist_tail):
+        if acc is not None:                                                # the scores of the clusters, where the matching reads them
+            conf_dev = [d['boxes'][r.reps[:r.k].long(), 0].contiguous() for d, r in zip(sc, c.rs)]
+        for bi, bth in enumerate(grid.mask_bin_th):
+            c.shared(bth)
+            if c.total:
+                _call('b2m_mask_hist_index_batch', c.extra_ptr, S, c.max_words, c.max_pts)
+            if acc is not None:
+                _match_stage(acc, grid, c.ci, bi, tabs, sc, c.cl, c.ksels, conf_dev, c.res, c.n_nms, c.total, c.o_lab, c.o_tail)
+                continue
+            host = c.res.cpu().numpy()                                     # the one host read of the stage
+            hoff = 0
+            for s_, (t, d, k) in enumerate(zip(tabs, sc, c.ksels)):
+                keep, label = c.split(host, s_)
+                inter = host[c.o_tail + hoff:c.o_tail + hoff + k * d['G']].reshape(k, d['G'])[:, :len(t.uniq)].astype(np.int64)
+                t.stages[-1].append(dict(label_id=label, inter=inter, keep=keep))
+                hoff += k * d['G']
+    return tabs
+
+
+def _hist_tail(c, sc):
+    """The scorer's part of a cluster stage for the ScanNet AP: the point histograms behind the labels, and the B2M_HIST_DESC table."""
+    hdesc = np.zeros((len(sc), 10), np.int64)
+    tb_all = torch.empty(max(sum(d['n_vox'] * ((k + 63) // 64) for k, d in zip(c.ksels, sc)), 1), dtype=torch.int64, device=c.dev)
+    n_hist = sum(k * d['G'] for k, d in zip(c.ksels, sc))
+
+    def fill(res):
+        toff = hoff = 0
+        for s_, (d, k) in enumerate(zip(sc, c.ksels)):
+            hdesc[s_] = (c.bits_ptr[s_], k, d['words'], d['n_vox'], d['v2p'].data_ptr(), d['dense32'].data_ptr(), d['n_pts'], d['G'],
+                         tb_all.data_ptr() + 8 * toff, res.data_ptr() + 4 * (c.o_tail + hoff))
+            toff += d['n_vox'] * ((k + 63) // 64); hoff += k * d['G']
+        return hdesc.reshape(-1), tb_all
+    return n_hist, fill
+
+
+class _ClusterStage:
+    """What the mask stages of ONE cluster_th share, for every scene of the batch: the clusters, the rows of the smallest score_th,
+    their bit rows and the result buffer ``res`` = keep flags (n_nms x total) | labels (total) | the scorer's tail, int32."""
+
+    def shared(self, bth):
+        """Projection, the mask NMS of every mask_nms_th and the labels of every projected row for one mask_bin_th."""
+        if self.total:
+            S = len(self.ksels)
+            _call('b2m_mask_project_batch', self.desc_ptr, S, self.total, self.max_words, float(bth))
+            _call('b2m_mask_nms_sweep_batch', self.desc_ptr, S, max(self.ksels), self.ths_nms.ctypes.data, self.n_nms, self.res.data_ptr(),
+                  self.total)
+            _call('b2m_label_hist_batch', self.desc_ptr, S, self.total, self.n_class)
+
+    def split(self, host, s_):
+        """(keep (n_nms, k) bool, label_id (k,) int32) of scene s_ from the host copy of ``res``."""
+        r0, k, total = self.row0[s_], self.ksels[s_], self.total
+        keep = np.stack([host[m * total + r0:m * total + r0 + k] for m in range(self.n_nms)], 0) != 0
+        return keep, host[self.o_lab + r0:self.o_lab + r0 + k].copy()
+
+
+def _cluster_stages(sc, grid, dev, tabs, n_class, tail):
+    """The front half every scorer shares: per cluster_th the clustering, the prefixes ``ks`` (appended to ``tabs``) and a
+    ``_ClusterStage``.  ``tail(c, sc)`` -> (number of int32 the scorer wants behind the labels, fill(res) -> (its int64 descriptor
+    table, whatever must stay alive)): the table rides behind the B2M_MASK_DESC table in the one upload, at ``c.extra_ptr``."""
+    S = len(sc)
     ths_nms = np.ascontiguousarray(grid.mask_nms_th, np.float32)           # C float, as float(mask_nms_th) becomes at the ABI
     n_nms = len(ths_nms)
     max_words, max_pts = max(d['words'] for d in sc), max(d['n_pts'] for d in sc)
     for cth in grid.cluster_th:
-        rs, cl = _cluster(sc, cth, grid.score_th)
-        for t, c in zip(tabs, cl):
-            t.clusters.append(c)
+        c = _ClusterStage()
+        c.rs, c.cl = _cluster(sc, cth, grid.score_th)
+        for t, cl_ in zip(tabs, c.cl):
+            t.clusters.append(cl_)
             t.stages.append([])
-        ci = len(tabs[0].clusters) - 1
-        if acc is not None:                                                # the scores of the clusters, where the matching reads them
-            conf_dev = [d['boxes'][r.reps[:r.k].long(), 0].contiguous() for d, r in zip(sc, rs)]
+        c.ci, c.dev, c.n_class, c.ths_nms, c.n_nms, c.max_words, c.max_pts = len(tabs[0].clusters) - 1, dev, n_class, ths_nms, n_nms, max_words, max_pts
         # rows no setting can keep are never projected: the prefix of the SMALLEST score_th (the grid is ascending)
-        ksels = [int(c['ks'][0]) for c in cl]
-        total = sum(ksels)
+        ksels = c.ksels = [int(cl_['ks'][0]) for cl_ in c.cl]
+        total = c.total = sum(ksels)
         sel_all = torch.cat([torch.arange(k, dtype=torch.int32) for k in ksels]).to(dev) if total else \
             torch.zeros(1, dtype=torch.int32, device=dev)
         bits_all = torch.empty(max(sum(k * max(d['words'], 1) for k, d in zip(ksels, sc)), 1), dtype=torch.int64, device=dev)
         inter_all = torch.empty(max(sum(k * k for k in ksels), 1), dtype=torch.int32, device=dev)
-        tb_all = torch.empty(max(sum(d['n_vox'] * ((k + 63) // 64) for k, d in zip(ksels, sc)), 1), dtype=torch.int64, device=dev)
-        # every result of a stage in ONE int32 buffer -- keep flags | labels | point histograms -- and one host read of it
-        n_hist = sum(k * d['G'] for k, d in zip(ksels, sc))
-        o_lab, o_hist = n_nms * total, n_nms * total + total
-        res = torch.zeros(max(o_hist + n_hist, 1), dtype=torch.int32, device=dev)
+        # every result of a stage in ONE int32 buffer -- keep flags | labels | the scorer's tail -- and one host read of it
+        c.o_lab, c.o_tail = n_nms * total, n_nms * total + total
+        c.bits_ptr, c.row0 = [], []
+        row0 = boff = 0
+        for d, k in zip(sc, ksels):
+            c.bits_ptr.append(bits_all.data_ptr() + 8 * boff)
+            c.row0.append(row0)
+            row0 += k; boff += k * max(d['words'], 1)
+        n_tail, fill = tail(c, sc)
+        res = c.res = torch.zeros(max(c.o_tail + n_tail, 1), dtype=torch.int32, device=dev)
         desc = np.zeros((S, 20), np.int64)
-        hdesc = np.zeros((S, 10), np.int64)
-        row0 = boff = ioff = toff = hoff = 0
-        for s_, (d, r, k) in enumerate(zip(sc, rs, ksels)):
-            bits_ptr = bits_all.data_ptr() + 8 * boff
+        ioff = 0
+        for s_, (d, r, k) in enumerate(zip(sc, c.rs, ksels)):
+            row0 = c.row0[s_]
             desc[s_, 0:10] = (r.heat.data_ptr(), d['n_fg'], sel_all.data_ptr() + 4 * row0, k, d['fg_slot'].data_ptr(),
-                              d['s2v'].data_ptr(), d['n_vox'], bits_ptr, d['words'], inter_all.data_ptr() + 4 * ioff)
-            desc[s_, 11:15] = (0, k, d['sem32'].data_ptr(), res.data_ptr() + 4 * (o_lab + row0))      # every projected row
+                              d['s2v'].data_ptr(), d['n_vox'], c.bits_ptr[s_], d['words'], inter_all.data_ptr() + 4 * ioff)
+            desc[s_, 11:15] = (0, k, d['sem32'].data_ptr(), res.data_ptr() + 4 * (c.o_lab + row0))      # every projected row
             desc[s_, 18:20] = (row0, row0)
-            hdesc[s_] = (bits_ptr, k, d['words'], d['n_vox'], d['v2p'].data_ptr(), d['dense32'].data_ptr(), d['n_pts'], d['G'],
-                         tb_all.data_ptr() + 8 * toff, res.data_ptr() + 4 * (o_hist + hoff))
-            row0 += k; boff += k * max(d['words'], 1); ioff += k * k; toff += d['n_vox'] * ((k + 63) // 64); hoff += k * d['G']
-        tables_dev = torch.from_numpy(np.concatenate([desc.reshape(-1), hdesc.reshape(-1)])).to(dev)
-        desc_ptr, hdesc_ptr = tables_dev.data_ptr(), tables_dev.data_ptr() + 8 * S * 20
+            ioff += k * k
+        extra, c.alive = fill(res)
+        tables_dev = c.tables_dev = torch.from_numpy(np.concatenate([desc.reshape(-1), extra])).to(dev)
+        c.desc_ptr, c.extra_ptr = tables_dev.data_ptr(), tables_dev.data_ptr() + 8 * S * 20
+        c.keep_alive = (sel_all, bits_all, inter_all)
+        yield c
+
+
+# ----------------------------------------------------------------------------------------------------------------- detection mAP
+class DetectionTables:
+    """What every setting of the grid needs of ONE scene to be scored with the oriented-box detection mAP, as host arrays.
+
+    clusters[ci]:    as ``SweepTables``;
+    gt_label (g,):   the classes of the scene's ground-truth boxes, in label order;
+    stages[ci][bi]:  label_id (K',) int32, keep (n_nms, K') bool, count (K',) int64 = scene POINTS in the row's mask, iou (K', g)
+                     float64 = box3d_iou (calc_iou without oriented boxes) of the row's prism with every same-class box, zero
+                     elsewhere and in the rows under ``min_points`` points; K' = ks[0]."""
+    __slots__ = ('name', 'n_pts', 'gt_label', 'min_points', 'clusters', 'stages')
+
+    def __init__(self, name, n_pts, gt_label, min_points):
+        self.name, self.n_pts, self.gt_label, self.min_points = name, n_pts, gt_label, min_points
+        self.clusters, self.stages = [], []
+
+
+def _detection_rows(tables, ci, si, bi, mi):
+    rows = compose(tables, ci, si, bi, mi)
+    return rows[tables.stages[ci][bi]['count'][rows] >= tables.min_points]
+
+
+def detection_records(tables, ci, si, bi, mi):
+    """The scene's ``{'label', 'conf', 'gt_label', 'iou'}`` record of one setting, as ``eval_detection.eval_det`` takes it: the rows
+    of ``compose`` with at least ``min_points`` points (evaluation.py:279-281: the gate comes after the mask NMS), in prediction
+    order."""
+    st = tables.stages[ci][bi]
+    rows = _detection_rows(tables, ci, si, bi, mi)
+    return {'label': st['label_id'][rows], 'conf': tables.clusters[ci]['conf'][rows], 'gt_label': tables.gt_label, 'iou': st['iou'][rows]}
+
+
+def _hull_tail(hs, cap):
+    """The scorer's part of a cluster stage for the detection mAP.  Behind the labels: flags | n_hull | ncand | count (``total``
+    int32 each), then, 8-byte aligned, the IoU tables of the scenes (k x g doubles each).  The B2M_HULLIDX_DESC table."""
+    def tail(c, sc):
+        c.o_side = c.o_tail
+        c.o_iou = c.o_tail + 4 * c.total
+        c.o_iou += c.o_iou & 1
+        c.scr = [dict(pbits=torch.empty(max(k * ((d['n_pts'] + 63) // 64), 1), dtype=torch.int64, device=c.dev),
+                      work=torch.empty(max(k, 1) * eval_detection.HULL_CHUNKS * eval_detection.HULL_PART, dtype=torch.float64, device=c.dev),
+                      box6=torch.empty((max(k, 1), 6), dtype=torch.float64, device=c.dev),
+                      hull=torch.empty((max(k, 1), eval_detection.HULL_MAX, 2), dtype=torch.float64, device=c.dev))
+                 for k, d in zip(c.ksels, sc)]
+        return c.o_iou - c.o_tail + 2 * sum(k * h['g'] for k, h in zip(c.ksels, hs)), lambda res: _hull_desc(c, sc, hs, cap)
+    return tail
+
+
+def _hull_desc(c, sc, hs, cap):
+    """B2M_HULLIDX_DESC table of a cluster stage with candidate buffers for ``cap`` (flat int64), and the buffers."""
+    dev = c.dev
+    cand = [torch.empty((max(k, 1), cap, 2), dtype=torch.float64, device=dev) for k in c.ksels]
+    stk = [torch.empty((max(k, 1), cap), dtype=torch.int32, device=dev) for k in c.ksels]
+    rec = np.zeros((len(sc), 17), np.int64)
+    side = lambda j, r0: c.res.data_ptr() + 4 * (c.o_side + j * c.total + r0)
+    for s_, (d, h, k, q) in enumerate(zip(sc, hs, c.ksels, c.scr)):
+        r0 = c.row0[s_]
+        rec[s_] = (c.bits_ptr[s_], k, d['words'], d['n_vox'], d['v2p'].data_ptr(), h['pos'].data_ptr(), d['n_pts'], q['pbits'].data_ptr(),
+                   q['work'].data_ptr(), cand[s_].data_ptr(), stk[s_].data_ptr(), side(2, r0), side(3, r0), q['box6'].data_ptr(),
+                   q['hull'].data_ptr(), side(1, r0), side(0, r0))
+    return rec.reshape(-1), (cand, stk)
+
+
+def detection_tables(net, batch, pred, cfg, grid, positions=None, labels=None, oriented_boxes=True,
+                     min_points=eval_detection.MIN_POINTS, cap=eval_detection.DEFAULT_CAP):
+    """``SelectionNet.detection2mask_detection_sweep``: one ``DetectionTables`` per scene of the batch.
+
+    positions: per scene (n_pts, 3), default ``batch['scene'][i]['positions']``; labels: per scene the ``per_instance_bb_*`` dict
+    ``eval_detection.gt_boxes`` takes, default ``batch['labels']``.  The prism of a projected row -- its point count, z range and
+    x-y hull -- and its IoU with the ground-truth boxes depend on (cluster_th, mask_bin_th) alone: one ``b2m_mask_hulls_index_batch``
+    and one IoU call per scene for each such stage, and ONE host read of the stage (keep flags, labels, hull flags, counts and the
+    IoU tables together).  A filled candidate buffer redoes the stage's hulls once with the capacity ``check_flags`` asks for; a
+    hull beyond B2M_HULL_MAX vertices in a row some setting keeps raises B2MError."""
+    _lib.require_gpu()
+    dev = torch.device('cuda', torch.cuda.current_device())
+    sc = _scene_inputs(net, batch, pred, cfg, dev)
+    if not sc:
+        return []
+    if cap < 64 or cap & (cap - 1):
+        raise ValueError('cap: a power of two >= 64, got %r' % (cap,))
+    S = len(sc)
+    n_class = int(max(int(net.semantic_valid_class_ids.max()) + 1, 1))
+    if labels is None:
+        labels = batch.get('labels')
+    if labels is None or len(labels) != S:
+        raise ValueError('the detection mAP needs the ground-truth boxes of every scene (labels / batch[\'labels\'])')
+    hs, tabs = [], []
+    for d in sc:
+        lab = labels[d['idx']]
+        if not isinstance(lab, dict) or any(k not in lab for k in ('per_instance_bb_centers', 'per_instance_bb_bounds', 'per_instance_semantics')):
+            raise ValueError('%s: labels without boxes (per_instance_bb_centers / _bounds, per_instance_semantics)' % d['name'])
+        p = positions[d['idx']] if positions is not None else batch['scene'][d['idx']].get('positions')
+        if p is None:
+            raise ValueError('%s: no positions' % d['name'])
+        p = eval_detection._f64(p, dev)
+        if p.dim() != 2 or tuple(p.shape) != (d['n_pts'], 3):
+            raise ValueError('%s: positions %s for %d points' % (d['name'], tuple(p.shape), d['n_pts']))
+        gt = eval_detection.gt_boxes(lab)                                  # once per scene
+        hs.append(dict(pos=p, gt=gt, g=gt['g']))
+        tabs.append(DetectionTables(d['name'], d['n_pts'], gt['label'], min_points))
+    for c in _cluster_stages(sc, grid, dev, tabs, n_class, _hull_tail(hs, cap)):
+        total, res = c.total, c.res
+        n_iou = sum(k * h['g'] for k, h in zip(c.ksels, hs))
+        iou_all = res[c.o_iou:c.o_iou + 2 * n_iou].view(torch.float64)
+        label_dev, count_dev = res[c.o_lab:c.o_lab + total], res[c.o_side + 3 * total:c.o_side + 4 * total]
+
+        def score(desc_ptr, cap_):
+            _call('b2m_mask_hulls_index_batch', desc_ptr, S, cap_, max(c.ksels), c.max_pts)
+            cls = torch.where(count_dev >= min_points, label_dev, torch.full_like(label_dev, -1))     # evaluation.py:279-281
+            ioff = 0
+            for s_, (h, k, q) in enumerate(zip(hs, c.ksels, c.scr)):
+                g, gt, r0 = h['g'], h['gt'], c.row0[s_]
+                if k and g:
+                    out = iou_all[ioff:ioff + k * g]
+                    side = lambda j: res.data_ptr() + 4 * (c.o_side + j * total + r0)
+                    if oriented_boxes:
+                        _call('b2m_hull_box_iou', q['hull'].data_ptr(), side(1), q['box6'].data_ptr(), cls[r0:r0 + k].data_ptr(), k,
+                              gt['boxes'].data_ptr(), gt['cls'].data_ptr(), g, out.data_ptr())
+                    else:
+                        _call('b2m_aabb_iou', q['box6'].data_ptr(), cls[r0:r0 + k].data_ptr(), k, gt['centers'].data_ptr(),
+                              gt['boxes'].data_ptr(), gt['cls'].data_ptr(), g, out.data_ptr())
+                ioff += k * g
+            return res.cpu().numpy()                                       # the one host read of the stage
+
+        def need_of(host):
+            """0, or the candidate capacity a second pass needs; rows no setting keeps are not looked at."""
+            if not oriented_boxes or not total:
+                return 0
+            used = host[:c.n_nms * total].reshape(c.n_nms, total).any(0)
+            side = host[c.o_side:c.o_side + 4 * total].reshape(4, total)
+            return eval_detection.check_flags(np.where(used, side[0], 0), side[1], np.where(used, side[2], 0))
+
         for bi, bth in enumerate(grid.mask_bin_th):
-            if total:
-                _call('b2m_mask_project_batch', desc_ptr, S, total, max_words, float(bth))
-                _call('b2m_mask_nms_sweep_batch', desc_ptr, S, max(ksels), ths_nms.ctypes.data, n_nms, res.data_ptr(), total)
-                _call('b2m_label_hist_batch', desc_ptr, S, total, n_class)
-                _call('b2m_mask_hist_index_batch', hdesc_ptr, S, max_words, max_pts)
-            if acc is not None:
-                _match_stage(acc, grid, ci, bi, tabs, sc, cl, ksels, conf_dev, res, n_nms, total, o_lab, o_hist)
-                continue
-            host = res.cpu().numpy()                                       # the one host read of the stage
-            row0 = hoff = 0
-            for t, d, k in zip(tabs, sc, ksels):
-                keep = np.stack([host[m * total + row0:m * total + row0 + k] for m in range(n_nms)], 0) != 0
-                inter = host[o_hist + hoff:o_hist + hoff + k * d['G']].reshape(k, d['G'])[:, :len(t.uniq)].astype(np.int64)
-                t.stages[-1].append(dict(label_id=host[o_lab + row0:o_lab + row0 + k].copy(), inter=inter, keep=keep))
-                row0 += k; hoff += k * d['G']
+            c.shared(bth)
+            host = score(c.extra_ptr, cap) if total else res.cpu().numpy()
+            need = need_of(host)
+            if need:                                                       # once more, with room for every candidate
+                rec, alive = _hull_desc(c, sc, hs, need)
+                again = torch.from_numpy(rec).to(dev)
+                host = score(again.data_ptr(), need)
+                if need_of(host):
+                    raise _lib.B2MError('hull candidates still exceed the buffer (%d)' % need)
+                del alive
+            iou_host = host[c.o_iou:c.o_iou + 2 * n_iou].view(np.float64)
+            ioff = 0
+            for s_, (t, h, k) in enumerate(zip(tabs, hs, c.ksels)):
+                keep, label = c.split(host, s_)
+                r0 = c.o_side + 3 * total + c.row0[s_]
+                t.stages[-1].append(dict(label_id=label, keep=keep, count=host[r0:r0 + k].astype(np.int64),
+                                         iou=iou_host[ioff:ioff + k * h['g']].reshape(k, h['g']).copy()))
+                ioff += k * h['g']
     return tabs
+
+
+def arkit_param_search(model, batches, grid, oriented_boxes=True, iou_t=0.5, per_class=False):
+    """Score every setting of ``grid`` with the ARKitScenes detection mAP (``eval_detection.arkitscenes_eval``) over all ``batches``.
+
+    batches: an iterable of batch dicts or ``(batch, pred)`` pairs; the scenes carry ``positions`` and ``batch['labels']`` the
+    boxes, as the reference's ARKitScenes loader returns them.  Returns dict(map (nc, ns, nb, nm), with a trailing axis when
+    ``iou_t`` is a sequence (the records do not depend on it); best = the setting with the largest mAP (of the first ``iou_t``),
+    NaN last, then grid order; best_ths; n_evaluated = the number of DISTINCT record sets matched; with per_class, ap_by_class =
+    {setting: {class id: AP}} (a tuple of such per ``iou_t`` for a sequence)).  Matching and the VOC AP are the unchanged
+    ``eval_detection.eval_det``, once per distinct record set."""
+    shape = grid.shape
+    settings = list(grid.settings())
+    many = not np.isscalar(iou_t)
+    ths = [float(v) for v in (iou_t if many else [iou_t])]
+    if not ths:
+        raise ValueError('iou_t: a threshold or a non-empty sequence of thresholds')
+    recs = {st: {} for st in settings}
+    keys = {st: [] for st in settings}
+    for item in batches:
+        batch, pred = item if isinstance(item, (tuple, list)) else \
+            (item, model.get_prediction(item, with_grad=False, to_cpu=True, min_size=True))
+        for t in model.pred2mask_detection_sweep(batch, pred, grid, oriented_boxes=oriented_boxes):
+            for st in settings:
+                recs[st][t.name] = detection_records(t, *st)
+                # two settings whose scenes score the same rows of the same (cluster_th, mask_bin_th) stage have the same records
+                keys[st].append((t.name, st[0], st[2], _detection_rows(t, *st).tobytes()))
+    out_map = np.full(shape + (len(ths),), np.nan)
+    by_class, done = {}, {}
+    for st in settings:
+        key = tuple(keys[st])
+        if key not in done:
+            aps = [eval_detection.eval_det(recs[st], ovthresh=th)[2] for th in ths]
+            done[key] = (aps, [float(eval_detection.mean_ap(ap)) for ap in aps])
+        aps, means = done[key]
+        out_map[st] = means
+        by_class[st] = tuple(aps) if many else aps[0]
+    rank = lambda st: -np.inf if np.isnan(out_map[st][0]) else out_map[st][0]
+    best = max(settings, key=lambda st: (rank(st), tuple(-i for i in st)))
+    out = dict(map=out_map if many else out_map[..., 0], best=best, best_ths=grid.eval_ths(*best), n_evaluated=len(done))
+    if per_class:
+        out['ap_by_class'] = by_class
+    return out
 
 
 def _match_stage(acc, grid, ci, bi, tabs, sc, cl, ksels, conf_dev, res, n_nms, total, o_lab, o_hist):

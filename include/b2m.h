@@ -685,6 +685,29 @@ int b2m_mask_hulls(const uint64_t* bits, int64_t words, int32_t k, const double*
                    int32_t* stk, int32_t cap, int32_t* ncand, int32_t* count, double* box6, double* hull, int32_t* n_hull,
                    int32_t* flags, void* stream);
 
+/* b2m_mask_hulls for masks that live on the scene's voxels and are asked about on its points (the threshold sweep scored with the
+ * detection mAP, box2mask_amd/param_search.py): point p < n_pts is in row r iff bit index[p] of bits[r] is set.  bits: k x words
+ * with words = ceil(n_vox / 64); index = vox2point, int64[n_pts]; pos[n_pts][3].  The contract for `index` is that of
+ * b2m_mask_hist_index: repeats allowed, voxels no point names allowed, a point whose index lies outside [0, n_vox) is in no mask,
+ * bits at or above n_vox are ignored, NULL = identity.  By definition what b2m_mask_gather, then b2m_mask_pack, then
+ * b2m_mask_hulls report, without the k x n_pts bytes: count, box6, ncand, hull, n_hull and flags with the same meaning and
+ * capacities; among equal extremes the smallest POINT index wins; nothing depends on chunking or on atomic order.
+ * pbits: scratch of k * ceil(n_pts / 64) uint64 (the rows over the points, one bit each, written here first; the three passes of
+ * b2m_mask_hulls then run over it).  The other scratch as for b2m_mask_hulls.  n_pts < 2^31, k <= 65535. */
+int b2m_mask_hulls_index(const uint64_t* bits, int64_t words, int32_t k, int64_t n_vox, const int64_t* index, const double* pos,
+                         int64_t n_pts, uint64_t* pbits, double* work, double* cand, int32_t* stk, int32_t cap, int32_t* ncand,
+                         int32_t* count, double* box6, double* hull, int32_t* n_hull, int32_t* flags, void* stream);
+/* The same for n_scenes scenes, one launch per pass (four in all).  `desc`: device array of n_scenes records of B2M_HULLIDX_DESC
+ * int64 fields (pointers stored as integers), the arguments of b2m_mask_hulls_index in this order without `cap`, which all scenes
+ * share:
+ *    0 bits   1 k   2 words   3 n_vox   4 index   5 pos   6 n_pts   7 pbits   8 work   9 cand   10 stk   11 ncand   12 count
+ *   13 box6   14 hull   15 n_hull   16 flags
+ * The caller keeps every record within the limits above (they are device memory; only the two maxima are checked here).
+ * max_k / max_pts = the largest k / n_pts of the table.  A scene with k = 0 writes nothing; one with n_pts = 0 writes what the
+ * single form writes for it (empty rows). */
+#define B2M_HULLIDX_DESC 17
+int b2m_mask_hulls_index_batch(const int64_t* desc, int32_t n_scenes, int32_t cap, int32_t max_k, int64_t max_pts, void* stream);
+
 /* Ground-truth boxes: centers[g][3], bounds[g][3] (half sizes), rotations[g][9] as labels['per_instance_bb_rotations'] stores
  * them (the corners use the TRANSPOSE of the row-major 3x3, evaluation.py:261).  boxes[g][B2M_OBB_REC]:
  *   0..7 x,y of corners 0..3 of get_oriented_corners    8 z of corner 0    9 z of corner 7    10 box3d_vol (box_util.py:87-92)

@@ -2,7 +2,7 @@
 path: scenes of ~150 k voxels from synth.make_batch, votes as bench.py's votes leg makes them (every segment votes for its object's
 box with 2.5 cm noise, score logits ~ N(0, 2)), the default 6 x 5 x 4 x 5 grid.
 
-    python tools/bench_param_sweep.py [--scenes 8] [--voxels 150000] [--loop-settings 12]
+    python tools/bench_param_sweep.py [--scenes 8] [--voxels 150000] [--loop-settings 12] [--metric scannet|arkit]
 
 Reports the device ms of the sweep's stages (HIP events round every launch, a pass of its own: the events serialise the stream),
 the wall time of the sweep up to the tables, the wall time of the host matching of all settings, and the looped path --
@@ -11,6 +11,11 @@ scaled to the grid (0 = every setting).  The looped settings' APs are compared w
 matching='device' (box2mask_amd/eval_match.py): its wall time up to the AP table beside the host route's of this very run, the
 device ms of its row-table, matching, sort and curve launches (HIP events round every launch, the median over `--device-runs`
 timed searches after a warm-up) and the largest difference between the two routes' averages.  One JSON line at the end.
+
+--metric arkit: the same scenes, votes and grid scored with the oriented-box detection mAP (param_search.arkit_param_search; the
+rooms' furniture boxes as ground truth): device ms per stage with the hull passes (b2m_mask_hulls_index_batch) and the IoU calls,
+the wall time of the tables and of the whole search, and the looped path -- Model.pred2mask + eval_detection.arkitscenes_eval per
+setting -- on `--loop-settings` settings, scaled to the grid, with its mAPs compared with the sweep's.
 """
 import argparse
 import json
@@ -31,6 +36,8 @@ from box2mask_amd.config import scannet_config                    # noqa: E402
 from box2mask_amd.model import Model                              # noqa: E402
 
 AP_STAGES = ('b2m_ap_rows', 'b2m_ap_match', 'b2m_sort_u64', 'b2m_ap_curve')
+ARKIT_STAGES = ('b2m_nmc_batch', 'b2m_mask_project_batch', 'b2m_mask_nms_sweep_batch', 'b2m_label_hist_batch',
+                'b2m_mask_hulls_index_batch', 'b2m_hull_box_iou')
 STAGES = ('b2m_nmc_batch', 'b2m_mask_project_batch', 'b2m_mask_nms_sweep_batch', 'b2m_label_hist_batch', 'b2m_mask_hist_index_batch')
 
 
@@ -48,10 +55,13 @@ def main(argv=None):
     ap.add_argument('--voxels', type=int, default=150000)
     ap.add_argument('--loop-settings', type=int, default=12, help='settings the looped path is timed on, scaled to the grid (0 = all)')
     ap.add_argument('--device-runs', type=int, default=5, help='timed searches with matching=device (median)')
+    ap.add_argument('--metric', choices=('scannet', 'arkit'), default='scannet')
     args = ap.parse_args(argv)
     cfg = scannet_config()
     model = Model(cfg, *synth.scannet_tables())
     model.eval()
+    if args.metric == 'arkit':
+        return arkit_leg(args, cfg, model)
     batch = synth.make_batch(args.scenes, seed0=0, target_voxels=args.voxels)
     pred, _ = synthetic_votes(batch, cfg)
     gts = {sc['name']: synth.gt_instance_ids(batch, b) for b, sc in enumerate(batch['scene'])}
@@ -155,6 +165,82 @@ def main(argv=None):
            'looped_settings_timed': len(chosen), 'looped_pred2mask_s': round(t_mask, 3), 'looped_compute_eval_s': round(t_eval, 3),
            'looped_scaled_to_grid_s': round((t_mask + t_eval) * scale, 1), 'looped_is_scaled': len(chosen) != n_set,
            'looped_ap_equals_sweep_ap': agree}
+    print(json.dumps(out))
+
+
+def arkit_leg(args, cfg, model):
+    from box2mask_amd import eval_detection
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    from train_synthetic import box_labels
+    batch = synth.make_batch(args.scenes, seed0=0, target_voxels=args.voxels)
+    pred, _ = synthetic_votes(batch, cfg)
+    # the layout of the ARKitScenes loader: the scenes carry the positions vox2point indexes, the batch the boxes
+    raws = [synth.make_scene(s, target_voxels=args.voxels, points_only=True) for s in range(args.scenes)]
+    for sc, raw, v2p in zip(batch['scene'], raws, batch['vox2point']):
+        assert len(raw['positions']) == len(v2p)
+        sc['positions'] = raw['positions']
+    batch['labels'] = [box_labels(r) for r in raws]
+    grid = param_search.ThresholdGrid.from_cfg(cfg)
+    n_set = int(np.prod(grid.shape))
+    note = lambda msg: print('[bench_param_sweep] ' + msg, file=sys.stderr, flush=True)
+    note('arkit: %d scenes, %d voxels, %d settings' % (args.scenes, batch['vox_coords'].shape[0], n_set))
+    model.pred2mask_detection_sweep(batch, pred, grid)                                  # warm-up
+    tabs, sweep_s = wall(lambda: model.pred2mask_detection_sweep(batch, pred, grid))
+    rec = []
+
+    def hook(name, a, meta=None):
+        if name not in ARKIT_STAGES:
+            return None
+        s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s_.record()
+
+        def done():
+            e_.record()
+            rec.append((name, s_, e_))
+        return done
+    _lib.set_hook(hook)
+    model.pred2mask_detection_sweep(batch, pred, grid)
+    torch.cuda.synchronize()
+    _lib.set_hook(None)
+    stages = {n: {'launches': 0, 'ms': 0.0} for n in ARKIT_STAGES}
+    for name, s_, e_ in rec:
+        stages[name]['launches'] += 1
+        stages[name]['ms'] += s_.elapsed_time(e_)
+    note('tables %.3f s; the whole search ...' % sweep_s)
+    res, search_s = wall(lambda: param_search.arkit_param_search(model, [(batch, pred)], grid))
+    note('search %.1f s; the looped path ...' % search_s)
+    settings = list(grid.settings())
+    n_loop = n_set if args.loop_settings <= 0 else min(args.loop_settings, n_set)
+    chosen = [settings[i] for i in np.unique(np.linspace(0, n_set - 1, n_loop).round().astype(int))]
+    saved, agree = cfg.eval_ths, True
+    model.cfg.eval_ths = grid.eval_ths(*chosen[0])
+    one = lambda r: eval_detection.arkitscenes_eval(r, batch['scene'], batch['labels'], oriented_boxes=True, iou_t=0.5, verbose=False)
+    one(model.pred2mask(batch, pred, 'eval'))                                           # warm-up
+    t_mask = t_eval = 0.0
+    for st in chosen:
+        model.cfg.eval_ths = grid.eval_ths(*st)
+        r, dt = wall(lambda: model.pred2mask(batch, pred, 'eval'))
+        t_mask += dt
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)
+            (m, _), dt = wall(lambda: one(r))
+        t_eval += dt
+        agree &= bool(np.array_equal(res['map'][st], m, equal_nan=True))
+    model.cfg.eval_ths = saved
+    scale = n_set / len(chosen)
+    hull = stages['b2m_mask_hulls_index_batch']
+    out = {'metric': 'arkit', 'scenes': args.scenes, 'voxels': int(batch['vox_coords'].shape[0]), 'points': int(sum(t.n_pts for t in tabs)),
+           'ground_truth_boxes': int(sum(len(t.gt_label) for t in tabs)), 'grid': list(grid.shape), 'settings': n_set,
+           'projected_rows_per_cluster_th': [int(sum(t.clusters[ci]['ks'][0] for t in tabs)) for ci in range(grid.shape[0])],
+           'stages': {n: {'launches': v['launches'], 'ms': round(v['ms'], 3)} for n, v in stages.items()},
+           'hull_ms_per_stage': round(hull['ms'] / max(hull['launches'], 1), 3),
+           'iou_ms_per_stage': round(stages['b2m_hull_box_iou']['ms'] / max(hull['launches'], 1), 3),
+           'stages_device_ms': round(sum(v['ms'] for v in stages.values()), 3),
+           'tables_wall_s': round(sweep_s, 4), 'search_wall_s': round(search_s, 3), 'host_matching_s': round(search_s - sweep_s, 3),
+           'distinct_record_sets_matched': res['n_evaluated'], 'best': res['best_ths'], 'best_map': float(res['map'][res['best']]),
+           'looped_settings_timed': len(chosen), 'looped_pred2mask_s': round(t_mask, 3), 'looped_arkitscenes_eval_s': round(t_eval, 3),
+           'looped_scaled_to_grid_s': round((t_mask + t_eval) * scale, 1), 'looped_is_scaled': len(chosen) != n_set,
+           'looped_map_equals_sweep_map': agree}
     print(json.dumps(out))
 
 

@@ -3,13 +3,17 @@ reference's `--param_search`, models/evaluation.py:353-366) scored with the Scan
 
     python tools/train_synthetic.py --scenes 4 --voxels 20000 --steps 200 --checkpoint-dir /tmp/b2m_ckpt
     python tools/param_search.py --checkpoint-dir /tmp/b2m_ckpt --scenes 4 --voxels 20000 [--batch-size 2] [--top 10] [--check 5]
-                                 [--matching host|device]
+                                 [--matching host|device] [--metric scannet|arkit]
 
 The scenes are train_synthetic's (seeds 0 .. scenes-1: it validates on the scenes it trains on).  Prints the best settings and the
 winner as an `eval_ths` line.  --check N re-evaluates N settings spread over the grid (the winner among them) through
 Model.pred2mask and eval_metric.compute_eval and compares the three averages: exactly with --matching host; with --matching
 device (matching, curves and AP of every setting on the device, box2mask_amd/eval_match.py) within 4 n 2^-53 + 2^-50, n = one more
 than three entries per predicted mask of the setting (the longest curve it can give).  A difference is an error.
+
+--metric arkit scores the same grid with the oriented-box detection mAP of ARKitScenes instead (param_search.arkit_param_search;
+the furniture boxes of the synthetic rooms as labels, train_synthetic.box_labels), and --check compares with Model.pred2mask +
+eval_detection.arkitscenes_eval: the mAP must be equal bit for bit.
 """
 import argparse
 import os
@@ -24,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
-from box2mask_amd import eval_metric, param_search, synth    # noqa: E402
+from box2mask_amd import eval_detection, eval_metric, param_search, synth    # noqa: E402
 from box2mask_amd.config import scannet_config                # noqa: E402
 from box2mask_amd.model import Model                          # noqa: E402
 import train_synthetic as T                                   # noqa: E402
@@ -39,6 +43,8 @@ def main(argv=None):
     ap.add_argument('--top', type=int, default=10, help='settings to print (0 = the whole table)')
     ap.add_argument('--check', type=int, default=0, help='settings to re-evaluate through Model.pred2mask + compute_eval')
     ap.add_argument('--matching', choices=('host', 'device'), default='host', help='where the matching and the AP of the settings run')
+    ap.add_argument('--metric', choices=('scannet', 'arkit'), default='scannet', help='ScanNet AP, or the ARKitScenes detection mAP')
+    ap.add_argument('--iou-t', type=float, default=0.5, help='--metric arkit: the IoU threshold of a match')
     for axis in param_search.AXES:
         ap.add_argument('--%s_search' % axis, nargs=3, type=float, default=None, metavar=('MIN', 'MAX', 'NUM'),
                         help='np.linspace triple (default: config.py, the reference\'s)')
@@ -61,6 +67,12 @@ def main(argv=None):
         pred = model.get_prediction(batch, with_grad=False, to_cpu=True, min_size=True)
         items.append((batch, pred))
         gts.update({r['name']: T.ground_truth_ids(r) for r in raws})
+        # the layout of the ARKitScenes loader: the scenes carry their positions, the batch the boxes
+        for sc, r in zip(batch['scene'], raws):
+            sc['positions'] = r['positions']
+        batch['labels'] = [T.box_labels(r) for r in raws]
+    if args.metric == 'arkit':
+        return arkit(args, model, grid, items, loaded)
     t0 = time.time()
     with warnings.catch_warnings():
         warnings.simplefilter('ignore', RuntimeWarning)
@@ -100,6 +112,43 @@ def main(argv=None):
                     all(abs(a - b) <= bound for a, b in zip(ap_[st], want) if not np.isnan(b))
             bad += not same
             print('check %s: sweep %s  single-setting path %s  %s' % (grid.eval_ths(*st), ap_[st].tolist(), want, ('equal' if args.matching == 'host' else 'within the bound') if same else 'DIFFERENT'))
+        if bad:
+            raise SystemExit('%d of %d settings differ from the single-setting path' % (bad, len(picks)))
+    return res
+
+
+def arkit(args, model, grid, items, loaded):
+    t0 = time.time()
+    res = param_search.arkit_param_search(model, items, grid, oriented_boxes=True, iou_t=args.iou_t)
+    dt = time.time() - t0
+    m = res['map']
+    settings = list(grid.settings())
+    ranked = sorted(settings, key=lambda st: (np.inf if np.isnan(m[st]) else -m[st], st))
+    print('checkpoint %s: %d settings (%s) over %d scenes in %.1f s, %d distinct record sets matched'
+          % (loaded[2], len(settings), ' x '.join(str(n) for n in grid.shape), args.scenes, dt, res['n_evaluated']))
+    print('cluster_th score_th mask_bin_th mask_nms_th |  mAP@%.2f' % args.iou_t)
+    for st in ranked[:args.top or len(ranked)]:
+        print('%10.3f %8.3f %11.3f %11.3f | %8.4f' % (tuple(grid.eval_ths(*st)) + (m[st],)))
+    assert ranked[0] == res['best']
+    print('best: eval_ths = %s' % ' '.join('%.3f' % v for v in res['best_ths']))
+    if args.check:
+        picks = [settings[i] for i in np.unique(np.linspace(0, len(settings) - 1, args.check).round().astype(int))]
+        if res['best'] not in picks:
+            picks[-1] = res['best']
+        bad = 0
+        for st in picks:
+            model.cfg.eval_ths = grid.eval_ths(*st)
+            results, scenes, labels = {}, [], []
+            for batch, pred in items:
+                results.update(model.pred2mask(batch, pred, 'eval'))
+                scenes += batch['scene']
+                labels += batch['labels']
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore', RuntimeWarning)
+                want, _ = eval_detection.arkitscenes_eval(results, scenes, labels, oriented_boxes=True, iou_t=args.iou_t, verbose=False)
+            same = np.array_equal(m[st], want, equal_nan=True)
+            bad += not same
+            print('check %s: sweep %r  single-setting path %r  %s' % (grid.eval_ths(*st), float(m[st]), float(want), 'equal' if same else 'DIFFERENT'))
         if bad:
             raise SystemExit('%d of %d settings differ from the single-setting path' % (bad, len(picks)))
     return res
