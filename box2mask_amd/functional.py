@@ -843,7 +843,19 @@ class _BatchNorm(torch.autograd.Function):
             invstd = torch.empty(c, dtype=torch.float32, device=dev)
             group = _sync_group() if sync else None
             small = n <= bn_small_rows() and c % 4 == 0 and x.stride(0) % 4 == 0
-        if small and group is not None:
+        # a rank without rows under SyncBN still takes part in the exchange -- zero sums, a count of 0 -- and takes its constants and
+        # running statistics from the peers' rows; no kernel runs on the empty tensors (half_train._BatchNormH does the same)
+        empty = training and group is not None and n == 0
+        if empty:
+            small = False
+            if residual is not None:
+                residual = _f32c(residual)
+            y = torch.empty_like(x)
+            stats = torch.zeros(2 * c + 1, dtype=torch.float64, device=dev)
+            count_dev = _bn_exchange(stats, 0, group)
+            _bn_finalize_global(stats.data_ptr(), count_dev, c,
+                                *_bn_consts(gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift))
+        elif small and group is not None:
             # SyncBN on a small map: the one-launch kernel cut in two, the ranks' column sums and row counts meet in between
             # (statistics -> ONE packed all-reduce -> finalize + apply): 2 launches + the collective instead of 5 + it
             if residual is not None:
@@ -880,14 +892,14 @@ class _BatchNorm(torch.autograd.Function):
         else:
             _call('b2m_bn_finalize', None, 1.0, None, c, _ptr(gamma), _ptr(beta), eps, momentum, running_mean.data_ptr(),
                   running_var.data_ptr(), None, None, scale.data_ptr(), shift.data_ptr())
-        if not small:
+        if not small and not empty:
             if residual is not None:
                 residual = _f32c(residual)
             y = torch.empty_like(x)
             _call('b2m_bn_apply', x.data_ptr(), x.stride(0), n, c, scale.data_ptr(), shift.data_ptr(), _ptr(residual),
                   residual.stride(0) if residual is not None else 0, 1 if relu else 0, y.data_ptr(), y.stride(0))
         ctx.training, ctx.relu, ctx.count, ctx.sync, ctx.count_dev = training, relu, count, sync, count_dev
-        ctx.small = small
+        ctx.small, ctx.empty = small, empty
         ctx.has_res = residual is not None
         if training:
             # without a fused residual the ReLU mask is the sign of fmaf(x, scale, shift): the backward recomputes it
@@ -930,7 +942,11 @@ class _BatchNorm(torch.autograd.Function):
                        mean.data_ptr(), invstd.data_ptr())
             mask = (relu, _ptr(mscale), _ptr(mshift))
             out = (dx.data_ptr(), dx.stride(0), _ptr(dres), dres.stride(0) if dres is not None else 0)
-            if small and group is not None and ctx.count_dev is not None:
+            if ctx.empty:
+                # no rows: nothing to the peers' sums, zero parameter gradients, an empty dx
+                dbeta.zero_(); dgamma.zero_()
+                _sync_all_reduce(torch.zeros(2 * c, dtype=torch.float64, device=dev), group)
+            elif small and group is not None and ctx.count_dev is not None:
                 # SyncBN on a small map: reduce (this rank's sums, parameter gradients from them) -> all-reduce -> apply
                 xchg = torch.empty(2 * c, dtype=torch.float64, device=dev)
                 _call('b2m_bn_small_bwd_phase', 1, *tensors, _ptr(gamma), *mask, dbeta.data_ptr(), dgamma.data_ptr(), None, 0, None, 0,
@@ -989,8 +1005,9 @@ class _BatchNormPair(torch.autograd.Function):
                     _bn_finalize_local(x, ts, partial, *consts)
             else:
                 # SyncBN: the local column sums of BOTH layers and the local row count in one packed all-reduce
-                stats = torch.empty(4 * c + 1, dtype=torch.float64, device=dev)
-                for j, (x, ts, consts) in enumerate(sides):
+                # (a rank without rows takes part with zero sums and a count of 0, and launches nothing on its empty tensors)
+                stats = (torch.empty if n else torch.zeros)(4 * c + 1, dtype=torch.float64, device=dev)
+                for j, (x, ts, consts) in enumerate(sides if n else ()):
                     _bn_local_sums(x, ts, c, partial, stats.data_ptr() + 8 * 2 * c * j)
                 count_dev = _bn_exchange(stats, n, group)
                 for j, (_, _, consts) in enumerate(sides):
@@ -1001,8 +1018,11 @@ class _BatchNormPair(torch.autograd.Function):
             _call('b2m_bn_finalize', None, 1.0, None, c, _ptr(gb), _ptr(bb), eps_b, mom_b, rmb.data_ptr(), rvb.data_ptr(),
                   None, None, scb.data_ptr(), shb.data_ptr())
         y = torch.empty_like(xa)
-        _call('b2m_bn_apply2', xa.data_ptr(), xa.stride(0), xb.data_ptr(), xb.stride(0), n, c, sca.data_ptr(), sha.data_ptr(),
-              scb.data_ptr(), shb.data_ptr(), 1 if relu else 0, y.data_ptr(), y.stride(0))
+        empty = training and count_dev is not None and n == 0
+        if not empty:
+            _call('b2m_bn_apply2', xa.data_ptr(), xa.stride(0), xb.data_ptr(), xb.stride(0), n, c, sca.data_ptr(), sha.data_ptr(),
+                  scb.data_ptr(), shb.data_ptr(), 1 if relu else 0, y.data_ptr(), y.stride(0))
+        ctx.empty = empty
         ctx.training, ctx.relu, ctx.sync, ctx.count, ctx.count_dev = training, relu, sync, float(n), count_dev
         if training:
             ctx.save_for_backward(xa, xb, y, ga, gb, mean_a, inv_a, mean_b, inv_b, ba, bb)
@@ -1036,6 +1056,12 @@ class _BatchNormPair(torch.autograd.Function):
         sums = torch.empty(3 * c, dtype=torch.float64, device=dev)
         dba, dga = _param_grad_slots(ba, ga, c, dev)
         dbb, dgb = _param_grad_slots(bb, gb, c, dev)
+        if ctx.empty:
+            for t in (dba, dga, dbb, dgb):
+                t.zero_()
+            _sync_all_reduce(torch.zeros(3 * c, dtype=torch.float64, device=dev), _sync_group())
+            return (_own(dxa, ctx.src_a), dga if need[1] else None, dba if need[2] else None, None, None,
+                    _own(dxb, ctx.src_b), dgb if need[6] else None, dbb if need[7] else None, None, None) + (None,) * 9
         _call('b2m_bn_bwd_reduce2', dy.data_ptr(), dy.stride(0), y.data_ptr(), y.stride(0), xa.data_ptr(), xa.stride(0),
               xb.data_ptr(), xb.stride(0), n, c, mean_a.data_ptr(), inv_a.data_ptr(), mean_b.data_ptr(), inv_b.data_ptr(),
               relu, partial.data_ptr(), sums.data_ptr())
@@ -1082,9 +1108,10 @@ class _BatchNormGroup(torch.autograd.Function):
         off = [0]
         for c in cs:
             off.append(off[-1] + 2 * c)
-        stats = torch.empty(off[-1] + 1, dtype=torch.float64, device=dev)
+        # (a rank without rows takes part with zero sums and a count of 0, and launches nothing on its empty tensors)
+        stats = (torch.empty if n else torch.zeros)(off[-1] + 1, dtype=torch.float64, device=dev)
         partial = torch.empty(2 * max(cs) * _RED_BLOCKS, dtype=torch.float64, device=dev)
-        for j, x in enumerate(xs):
+        for j, x in enumerate(xs if n else ()):
             _bn_local_sums(x, None, cs[j], partial, stats.data_ptr() + 8 * off[j])
         count_dev = _bn_exchange(stats, n, group)
         ys, saved = [], []
@@ -1096,7 +1123,8 @@ class _BatchNormGroup(torch.autograd.Function):
             _bn_finalize_global(stats.data_ptr() + 8 * off[j], count_dev, c,
                                 *_bn_consts(gamma, beta, eps, mom, rm, rv, mean, invstd, scale, shift))
             y = torch.empty_like(x)
-            _call('b2m_bn_apply', x.data_ptr(), x.stride(0), n, c, scale.data_ptr(), shift.data_ptr(), None, 0, 0, y.data_ptr(), y.stride(0))
+            if n:
+                _call('b2m_bn_apply', x.data_ptr(), x.stride(0), n, c, scale.data_ptr(), shift.data_ptr(), None, 0, 0, y.data_ptr(), y.stride(0))
             ys.append(y)
             saved += [x, gamma, beta, mean, invstd]
         ctx.save_for_backward(*saved)
@@ -1109,7 +1137,7 @@ class _BatchNormGroup(torch.autograd.Function):
         m, n, cs, off = ctx.m, ctx.n, ctx.cs, ctx.off
         sv = ctx.saved_tensors
         dev = sv[0].device
-        sums = torch.empty(off[-1], dtype=torch.float64, device=dev)
+        sums = (torch.empty if n else torch.zeros)(off[-1], dtype=torch.float64, device=dev)
         partial = torch.empty(2 * max(cs) * _RED_BLOCKS, dtype=torch.float64, device=dev)
         dys = [_f32c(d) for d in dys]
         pg = []
@@ -1118,8 +1146,11 @@ class _BatchNormGroup(torch.autograd.Function):
             c = cs[j]
             dbeta, dgamma = _param_grad_slots(beta, gamma, c, dev)
             # (this rank's sums -> its parameter gradients; the gradient all-reduce averages those over the ranks)
-            _call('b2m_bn_bwd_reduce', dys[j].data_ptr(), dys[j].stride(0), None, 0, x.data_ptr(), x.stride(0), n, c, mean.data_ptr(),
-                  invstd.data_ptr(), 0, None, None, partial.data_ptr(), sums.data_ptr() + 8 * off[j], dbeta.data_ptr(), dgamma.data_ptr())
+            if n:
+                _call('b2m_bn_bwd_reduce', dys[j].data_ptr(), dys[j].stride(0), None, 0, x.data_ptr(), x.stride(0), n, c, mean.data_ptr(),
+                      invstd.data_ptr(), 0, None, None, partial.data_ptr(), sums.data_ptr() + 8 * off[j], dbeta.data_ptr(), dgamma.data_ptr())
+            else:
+                dbeta.zero_(); dgamma.zero_()
             pg.append((dgamma, dbeta))
         gsums = sums.clone()
         _sync_all_reduce(gsums, ctx.group)
@@ -1128,9 +1159,10 @@ class _BatchNormGroup(torch.autograd.Function):
             x, gamma, beta, mean, invstd = sv[5 * j:5 * j + 5]
             c = cs[j]
             dx = torch.empty_like(x)
-            _call('b2m_bn_bwd_apply', dys[j].data_ptr(), dys[j].stride(0), None, 0, x.data_ptr(), x.stride(0), n, c, mean.data_ptr(),
-                  invstd.data_ptr(), _ptr(gamma), gsums.data_ptr() + 8 * off[j], float(n), ctx.count_dev.data_ptr(), 0, None, None,
-                  dx.data_ptr(), dx.stride(0), None, 0)
+            if n:
+                _call('b2m_bn_bwd_apply', dys[j].data_ptr(), dys[j].stride(0), None, 0, x.data_ptr(), x.stride(0), n, c, mean.data_ptr(),
+                      invstd.data_ptr(), _ptr(gamma), gsums.data_ptr() + 8 * off[j], float(n), ctx.count_dev.data_ptr(), 0, None, None,
+                      dx.data_ptr(), dx.stride(0), None, 0)
             base = 2 + 7 * j
             out += [_own(dx, ctx.srcs[j]), pg[j][0] if ctx.needs_input_grad[base + 1] else None,
                     pg[j][1] if ctx.needs_input_grad[base + 2] else None, None, None, None, None]

@@ -200,10 +200,16 @@ class MinkowskiBatchNorm(nn.Module):
             self._affine_cache = cached
         return cached[1]
 
+    def _synced(self) -> bool:
+        """The statistics are those of all ranks' rows: this rank's own row count says nothing about them.  One local row (or
+        none) is then a batch like any other -- torch.nn.SyncBatchNorm asks for more than one value per channel over ALL ranks --
+        and a rank that raised here would leave its peers waiting in the exchange."""
+        return bool(self.sync) and F_._sync_group() is not None
+
     def apply_bn(self, feats, residual=None, relu=False, count_key=None, defer_counter=False):
         bn = self.bn
         training = self.training or not bn.track_running_stats
-        if training and feats.shape[0] == 1:   # torch.nn.functional.batch_norm raises the same (BatchNorm1d)
+        if training and feats.shape[0] == 1 and not self._synced():   # torch.nn.functional.batch_norm raises the same (BatchNorm1d)
             raise ValueError('Expected more than 1 value per channel when training, got input size %s'
                              % (tuple(feats.shape),))
         if self.training and bn.track_running_stats and bn.num_batches_tracked is not None:
@@ -230,7 +236,7 @@ class MinkowskiBatchNorm(nn.Module):
         """The bookkeeping of apply_bn for a layer that runs inside a paired operator: (training?, parameter tuple)."""
         bn = self.bn
         training = self.training or not bn.track_running_stats
-        if training and feats.shape[0] == 1:
+        if training and feats.shape[0] == 1 and not self._synced():
             raise ValueError('Expected more than 1 value per channel when training, got input size %s'
                              % (tuple(feats.shape),))
         if self.training and bn.track_running_stats and bn.num_batches_tracked is not None:
@@ -271,12 +277,16 @@ def batch_norm_group(norms, tensors):
     (functional._BatchNormGroup); otherwise -- a single process, eval mode, one member, B2M_BN_GROUP=0 -- every layer by itself."""
     import os
     sync = F_._sync_group() if all(nm.sync for nm in norms) else None
-    same_rows = len({t.F.shape[0] for t in tensors}) == 1
-    ok = (sync is not None and len(norms) > 1 and same_rows and all(nm.training for nm in norms) and
-          all(t.F.shape[1] % 4 == 0 and t.F.shape[1] <= 1024 for t in tensors) and tensors[0].F.shape[0] > 1 and
+    # Grouped or layer by layer decides HOW MANY exchanges this rank issues, and of what size: every rank has to decide alike, so
+    # only what all ranks share may enter -- the layers' flags, the channel counts, the switch.  Never this rank's row count: a
+    # rank with one pooled row (or none) that went layer by layer would issue 2m small exchanges against its peers' two packed ones.
+    ok = (sync is not None and len(norms) > 1 and all(nm.training for nm in norms) and
+          all(t.F.shape[1] % 4 == 0 and t.F.shape[1] <= 1024 for t in tensors) and
           os.environ.get('B2M_BN_GROUP', '1') == '1')
     if not ok:
         return [nm(t) for nm, t in zip(norms, tensors)]
+    if len({t.F.shape[0] for t in tensors}) != 1:
+        raise ValueError('batch_norm_group: the layers of a group see the same rows, got %s' % ([t.F.shape[0] for t in tensors],))
     members = []
     for nm, t in zip(norms, tensors):
         training, (w, b, rm, rv, mom, eps) = nm._begin(t.F, _defer_all[0])

@@ -4,7 +4,8 @@ fused residual add and ReLU (the reference's models/resnet.py:61-83: MinkowskiBa
 (models/detection_net.py:345-352: global pooling by pooling id), ReLU and add -- together with the error bounds the kernels are
 held to and the seeded cases shared by tests/test_norm_rule.py (CPU: the rule against float64 torch, the bounds against an fp32
 evaluation in another order and against deliberate mistakes) and tests/test_gpu_norm.py (the kernels against the rule).  The last
-section holds the binary16 BatchNorm kernels and the grouped SyncBN operator to the same rule (tests/test_gpu_norm_half.py).
+section but one holds the binary16 BatchNorm kernels and the grouped SyncBN operator to the same rule (tests/test_gpu_norm_half.py),
+the last one the SyncBN operators over ranks that hold DIFFERENT rows (tests/test_gpu_syncbn_ranks.py, profiles/syncbn_ranks_rule.md).
 
 Everything is numpy float64 on the fp32 inputs widened exactly; column statistics are two-pass (mean, then the mean of the
 squared deviations).  Inputs contain no -0.0, no NaN and no infinity: the packed atomic max of the kernel orders -0.0 below
@@ -911,3 +912,415 @@ def bn_emulate_h(inp, spec, mistake=None, pgs=1.0):
     if spec['res']:
         got['dres'] = rnd(g)
     return got
+
+
+# ================================================================== SyncBN over ranks that hold DIFFERENT rows
+# W ranks hold x_0 .. x_{W-1} (n_r rows each, any of them possibly none) of one batch X = [x_0; ...; x_{W-1}], N = sum n_r, with the
+# incoming gradients DY and residuals stacked alike.  The operators exchange (sum x, sum x^2, n_r) forward and (sum g, sum g xhat)
+# backward, each packed into ONE fp64 all-reduce, and document:
+#     constants, running statistics   the rule's on X, with N in the unbiased factor -- the same on every rank;
+#     y_r, dx_r                       the row slices of the rule's y and dx on X (dx with the sums over ALL rows, over N);
+#     dbeta_r, dgamma_r               the sums over rank r's rows only, with the global xhat (the gradient all-reduce averages the
+#                                     parameter gradients over the ranks afterwards, like every other gradient).
+# The bounds are the one-rank bounds with what the exchange adds:
+#     constants   const_bounds(X), its fp64 depth term raised by W: an element of rank r passes through at most min(n_r + 4, 288) <=
+#                 min(N + 4, 288) fp64 additions on its rank and at most W more where the packed sums meet (rank order), so
+#                 d = (min(N + 4, 288) + W) 2^-53 in const_bounds' formulas;
+#     y           y_bound with those constants;
+#     dbeta_r, dgamma_r   _grad_bounds on rank r's rows with the chain length L_r of the path that rank took (1: the small-map
+#                 half-kernels, every term added in fp64; 64: the two-stage kernels; chain_len(n_r, c) for the binary16 kernels) -- the
+#                 global mean's own error enters through the 3 u |mean| invstd term exactly as on one rank;
+#     dx_r        _grad_bounds' formula with the carried terms of ALL ranks: the device forms fl(fl32(S) / N) from S = sum_r S_r (fp64,
+#                 W - 1 more additions at 2^-53, nothing against the 3 u of margin), and S_r is off by at most B_r:
+#                     |gamma invstd| (8 u (|g| + |gbar| + |xhat gxbar| + |mean| invstd |gxbar|) + sum_r B_dbeta_r / N + |xhat| sum_r B_dgamma_r / N)
+#                 with gbar = |sum g| / N and gxbar = |sum g xhat| / N over all rows;
+#     binary16    one store more (half_store), the mask conventions and param_grad_scale of bn_check_half.
+RANK_SPREAD = (0.0, 3.0, 0.3, 10.0)       # distance between neighbouring ranks' column means, in units of the column's sigma
+
+
+def bn_input_ranks(rows, c, seed=0, half=False):
+    """bn_input for ranks of rows[r] rows each -> one dict per rank (x, res, dy of that rank; gamma, beta, rm0, rv0 shared).  The
+    column means differ between the ranks: rank r's column j is moved by (r - (W - 1) / 2) * RANK_SPREAD[(j + j // 8) % 4] sigma_j (a
+    constant column, sigma = 0, by that many units), so that in a quarter of the columns the spread BETWEEN the ranks is 25 times
+    the variance within one, in another quarter about twice, and in one quarter the ranks agree."""
+    world, total = len(rows), int(sum(rows))
+    base = bn_input(total, c, seed)
+    lo = np.concatenate([[0], np.cumsum(rows)]).astype(int)
+    step = np.array([RANK_SPREAD[(j + j // 8) % 4] * (_KIND[kind_of(j)][1] or 1.0) for j in range(c)])
+    out = []
+    for r in range(world):
+        sl = slice(lo[r], lo[r + 1])
+        d = dict(base)
+        d['x'] = np.ascontiguousarray((base['x'][sl].astype(np.float64) + (r - (world - 1) / 2.0) * step).astype(np.float32))
+        d['res'], d['dy'] = np.ascontiguousarray(base['res'][sl]), np.ascontiguousarray(base['dy'][sl])
+        if half:
+            for k in ('x', 'res', 'dy'):
+                d[k] = to_half(d[k])
+        out.append(d)
+    return out
+
+
+def _stack(inps, k):
+    return np.concatenate([f64(i[k]) for i in inps], 0)
+
+
+def bn_ranks_rule(inps, spec, mask=None):
+    """What every rank holds after the layer, in float64: one dict per rank (the constants and running statistics of X; y, dx, dres
+    as row slices; dbeta, dgamma over the rank's own rows).  mask: the ReLU decisions of all rows (default: the rule's own)."""
+    p = inps[0]
+    lo = np.concatenate([[0], np.cumsum([i['x'].shape[0] for i in inps])]).astype(int)
+    x_all = _stack(inps, 'x')
+    fwd = bn_forward(x_all, p['gamma'], p['beta'], _stack(inps, 'res') if spec['res'] else None, spec['relu'], (p['rm0'], p['rv0']))
+    if mask is None and spec['relu']:
+        mask = (fwd['pre'] > 0).astype(np.float64)
+    bwd = bn_backward(x_all, p['gamma'], fwd, _stack(inps, 'dy'), mask)
+    out = []
+    for r in range(len(inps)):
+        sl = slice(lo[r], lo[r + 1])
+        d = {k: fwd[k] for k in CONSTS}
+        d.update(y=fwd['y'][sl], dx=bwd['dx'][sl], dbeta=bwd['g'][sl].sum(0), dgamma=(bwd['g'][sl] * bwd['xhat'][sl]).sum(0))
+        if spec['res']:
+            d['dres'] = bwd['dres'][sl]
+        out.append(d)
+    return out
+
+
+def const_bounds_ranks(x_all, gamma, fwd, world):
+    """const_bounds on the union batch with its fp64 depth d = min(N + 4, 288) raised to d + W (every fp64 term is linear in d)."""
+    cb = const_bounds(x_all, gamma, fwd)
+    d0 = float(min(f64(x_all).shape[0] + 4, F64_DEPTH))
+    up = (d0 + world) / d0
+    out = {k: cb[k] * up for k in ('_dscale64', '_dshift64')}
+    for k in CONSTS:
+        if k in cb:
+            round_once = 2 * ulp32(fwd[k])
+            out[k] = round_once + np.maximum(cb[k] - round_once, 0.0) * up
+    return out
+
+
+def _ranks_grad_rows(sfx, inps, gamma, fwd, bwd, gots, chains, half=False, pgs=1.0):
+    """The rows of check() for dbeta_r, dgamma_r, dx_r (names + sfx) of every rank; bwd: bn_backward on the union batch."""
+    rows_n = [i['x'].shape[0] for i in inps]
+    lo = np.concatenate([[0], np.cumsum(rows_n)]).astype(int)
+    total = int(lo[-1])
+    c = f64(gamma).shape[0]
+    s = float(np.float32(pgs))
+    per, sum_db, sum_dg = [], np.zeros(c), np.zeros(c)
+    for r, inp in enumerate(inps):
+        sl = slice(lo[r], lo[r + 1])
+        g, xh = bwd['g'][sl], bwd['xhat'][sl]
+        mine = {'g': g, 'xhat': xh, 'dbeta': g.sum(0), 'dgamma': (g * xh).sum(0)}
+        if rows_n[r]:
+            gb = _grad_bounds(inp['x'], gamma, fwd, mine, chains[r])
+            b_db, b_dg = gb['dbeta'], gb['dgamma']
+        else:
+            b_db, b_dg = np.zeros(c), np.zeros(c)
+        sum_db, sum_dg = sum_db + b_db, sum_dg + b_dg
+        per.append((mine, b_db, b_dg))
+    g, xhat = np.abs(bwd['g']), np.abs(bwd['xhat'])
+    mi = np.abs(fwd['mean']) * fwd['invstd']
+    gi = np.abs(f64(gamma) * fwd['invstd'])
+    gbar, gxbar = np.abs(bwd['dbeta']) / total, np.abs(bwd['dgamma']) / total
+    b_dx = gi * (8 * U * (g + gbar + xhat * gxbar + mi * gxbar) + sum_db / total + xhat * sum_dg / total)
+    if half:
+        b_dx = half_store(bwd['dx'], b_dx)
+    rows = []
+    for r in range(len(inps)):
+        sl = slice(lo[r], lo[r + 1])
+        mine, b_db, b_dg = per[r]
+        for k, b in (('dbeta', b_db), ('dgamma', b_dg)):
+            if k + sfx in gots[r]:
+                b = b * s
+                if not is_pow2(s):
+                    b = b + U * (np.abs(mine[k]) * s + b)
+                rows.append(('%s%s[%d]' % (k, sfx, r), gots[r][k + sfx], mine[k] * s, b))
+        if 'dx' + sfx in gots[r]:
+            rows.append(('dx%s[%d]' % (sfx, r), gots[r]['dx' + sfx], bwd['dx'][sl], b_dx[sl]))
+    return rows
+
+
+def bn_ranks_check(tag, inps, spec, gots, chains, half=False, pgs=1.0, quiet=False):
+    """One SyncBN layer over ranks with different rows (see the section's head).  inps: bn_input_ranks(...); spec: res, relu;
+    gots[r]: what rank r produced (names as in bn_check / bn_check_half; absent names are not checked); chains[r]: the fp32 chain
+    length of the path rank r took.  The ReLU mask is the device's own -- the stacked y > 0, or the stacked 'mask' of a binary16 run
+    without a residual -- and must be the rule's outside the borderline elements.  -> (failures, share of borderline elements)."""
+    relu, has_res = spec['relu'], spec['res']
+    world = len(inps)
+    rows_n = [i['x'].shape[0] for i in inps]
+    lo = np.concatenate([[0], np.cumsum(rows_n)]).astype(int)
+    p = inps[0]
+    x_all, dy_all = _stack(inps, 'x'), _stack(inps, 'dy')
+    res_all = _stack(inps, 'res') if has_res else None
+    if half:
+        for i in inps:
+            for k in ('x', 'res', 'dy'):
+                assert np.array_equal(to_half(i[k]), i[k]), '%s is not binary16' % k
+    fwd = bn_forward(x_all, p['gamma'], p['beta'], res_all, relu, (p['rm0'], p['rv0']))
+    cb = const_bounds_ranks(x_all, p['gamma'], fwd, world)
+    yb = y_bound(x_all, fwd, res_all, cb)
+    y_store = half_store(fwd['y'], yb) if half else yb
+    rows = []
+    for r in range(world):
+        rows += [('%s[%d]' % (k, r), gots[r][k], fwd[k], cb[k]) for k in CONSTS if k in gots[r]]
+        rows.append(('y[%d]' % r, gots[r]['y'], fwd['y'][lo[r]:lo[r + 1]], y_store[lo[r]:lo[r + 1]]))
+    bad, share, mask = [], 0.0, None
+    if relu:
+        if half and not has_res:
+            mask = np.concatenate([np.asarray(g['mask'], dtype=bool).reshape(-1, x_all.shape[1]) for g in gots], 0)
+            edge = np.abs(fwd['pre']) <= yb
+        else:
+            mask = np.concatenate([f64(g['y']) for g in gots], 0) > 0
+            edge = np.abs(fwd['pre']) <= yb + (H_TINY if half else 0.0)
+        share = float(edge.mean())
+        wrong = (mask != (fwd['pre'] > 0)) & ~edge
+        if wrong.any():
+            bad.append('ReLU mask differs in %d elements that are not borderline' % int(wrong.sum()))
+    if any('dx' in g or 'dbeta' in g for g in gots):
+        bwd = bn_backward(x_all, p['gamma'], fwd, dy_all, mask.astype(np.float64) if mask is not None else None)
+        rows += _ranks_grad_rows('', inps, p['gamma'], fwd, bwd, gots, chains, half, pgs)
+        for r in range(world):
+            if gots[r].get('dres') is not None:
+                rows.append(('dres[%d]' % r, gots[r]['dres'], bwd['dres'][lo[r]:lo[r + 1]], None))
+    return check(tag, rows, bad, quiet), share
+
+
+def bn_ranks_check_half(tag, inps, spec, gots, pgs=1.0, quiet=False):
+    """bn_ranks_check for half_train.batch_norm: binary16 x / residual / dy / y / dx / dres, the chain of every rank from its launch
+    geometry (chain_len; a rank without rows launches nothing), dbeta / dgamma already multiplied by pgs."""
+    c = inps[0]['x'].shape[1]
+    chains = [chain_len(i['x'].shape[0], c) if i['x'].shape[0] else 1 for i in inps]
+    return bn_ranks_check(tag, inps, spec, gots, chains, half=True, pgs=pgs, quiet=quiet)
+
+
+def pair_ranks_check(tag, a_inps, b_inps, relu, gots, quiet=False):
+    """relu?(BN_a(xa) + BN_b(xb)) over ranks with different rows (functional.batch_norm_pair: the two-stage skeleton on every rank,
+    4c + 1 doubles forward, 3c backward).  gots[r]: y, dx_a, dx_b, dbeta_a, ... as in pair_check.  The incoming gradient is a's dy."""
+    world = len(a_inps)
+    rows_n = [i['x'].shape[0] for i in a_inps]
+    lo = np.concatenate([[0], np.cumsum(rows_n)]).astype(int)
+    side = {}
+    for s, inps in (('a', a_inps), ('b', b_inps)):
+        p = inps[0]
+        x_all = _stack(inps, 'x')
+        f = bn_forward(x_all, p['gamma'], p['beta'], None, False, (p['rm0'], p['rv0']))
+        side[s] = (inps, x_all, f, const_bounds_ranks(x_all, p['gamma'], f, world))
+    (_, xa, fa, ca), (_, xb, fb, cb) = side['a'], side['b']
+    pre = fa['y'] + fb['y']
+    y = np.maximum(pre, 0.0) if relu else pre
+    yb = 4 * U * (np.abs(xa * fa['scale']) + np.abs(fa['shift']) + np.abs(xb * fb['scale']) + np.abs(fb['shift']) + np.abs(y)) \
+        + np.abs(xa) * ca['_dscale64'] + ca['_dshift64'] + np.abs(xb) * cb['_dscale64'] + cb['_dshift64']
+    rows = []
+    for r in range(world):
+        rows.append(('y[%d]' % r, gots[r]['y'], y[lo[r]:lo[r + 1]], yb[lo[r]:lo[r + 1]]))
+        for s in 'ab':
+            _, _, f, cbs = side[s]
+            rows += [('%s_%s[%d]' % (k, s, r), gots[r][k + '_' + s], f[k], cbs[k]) for k in CONSTS if k + '_' + s in gots[r]]
+    bad, share, m = [], 0.0, None
+    if relu:
+        mask = np.concatenate([f64(g['y']) for g in gots], 0) > 0
+        edge = np.abs(pre) <= yb
+        share = float(edge.mean())
+        wrong = (mask != (pre > 0)) & ~edge
+        if wrong.any():
+            bad.append('ReLU mask differs in %d elements that are not borderline' % int(wrong.sum()))
+        m = mask.astype(np.float64)
+    dy_all = _stack(a_inps, 'dy')
+    for s in 'ab':
+        inps, x_all, f, _ = side[s]
+        bwd = bn_backward(x_all, inps[0]['gamma'], f, dy_all, m)
+        rows += _ranks_grad_rows('_' + s, inps, inps[0]['gamma'], f, bwd, gots, [CHAIN['two_stage']] * world)
+    return check(tag, rows, bad, quiet), share
+
+
+def group_ranks_check(tag, member_inps, gots, quiet=False):
+    """The members of a SyncBN group over ranks with different rows: each one the single layer's rule (no ReLU, no residual, the
+    two-stage kernels).  member_inps[j]: bn_input_ranks of member j; gots[j][r]: what rank r produced for member j."""
+    bad = []
+    for j, inps in enumerate(member_inps):
+        b, _ = bn_ranks_check('%s[%d]' % (tag, j), inps, {'relu': False, 'res': False}, gots[j], [CHAIN['two_stage']] * len(inps),
+                              quiet=quiet)
+        bad += ['member %d: %s' % (j, t) for t in b]
+    return bad
+
+
+def rank_chains(rows, small_rows):
+    """The fp32 chain length of the path functional._BatchNorm takes on every rank: the small-map half-kernels (1) up to small_rows
+    rows, the two-stage kernels (64) above."""
+    return [CHAIN['one_launch'] if n <= small_rows else CHAIN['two_stage'] for n in rows]
+
+
+def _rank_cases():
+    cases = {}
+
+    def add(rows, c, res, relu, small_rows=2048, **kw):
+        name = 'ranks-' + '+'.join(str(n) for n in rows) + '-c%d-res%d-relu%d' % (c, res, relu) + \
+            ('-small%d' % small_rows if small_rows != 2048 else '') + ('-' + kw['note'] if kw.get('note') else '')
+        cases[name] = dict(rows=tuple(rows), c=c, res=bool(res), relu=bool(relu), small_rows=small_rows, seed=4000 + len(cases), **kw)
+    add((300, 300), 32, 1, 1)                                  # equal counts, different rows
+    add((300, 300), 96, 0, 0, window=1, note='window')         # ... rank 1's x a column window of a wider tensor
+    add((1, 300), 96, 0, 1)                                    # one rank with a single row
+    add((2048, 2049), 32, 1, 1)                                # straddles bn_small_rows(): the half-kernels against the two-stage path
+    add((256, 257), 96, 0, 1, small_rows=256)                  # the same straddle at B2M_BN_SMALL_ROWS = 256
+    add((0, 257), 32, 1, 1)                                    # a rank without rows
+    add((1, 1), 4, 0, 0)                                       # N = 2
+    add((65, 1, 4033), 256, 0, 1, tiles=2)                     # three ranks; the large one's sums from per-tile sums
+    return cases
+
+
+RANK_CASES = _rank_cases()
+# binary16 (half_train.batch_norm): rows, c, res, relu.  (ReLU with a fused residual: the mask is the stored y's, which the operator
+# returns; without one it is the kernel's own recomputation, which only the C entries can be asked for -- tests/test_gpu_norm_half.py)
+HALF_RANK_CASES = {'ranks_h-1+300-c512-res1-relu1': ((1, 300), 512, True, True, 4100),
+                   'ranks_h-0+257-c32-res1-relu1': ((0, 257), 32, True, True, 4101),
+                   'ranks_h-65+1+4033-c96-res0-relu0': ((65, 1, 4033), 96, False, False, 4102)}
+# the pair: rows, c, relu
+PAIR_RANK_CASES = {'pair_ranks-300+300-c32': ((300, 300), 32, True, 4200), 'pair_ranks-1+300-c96': ((1, 300), 96, True, 4201),
+                   'pair_ranks-0+257-c4': ((0, 257), 4, False, 4202)}
+# the group: rows; the members' channel counts are GROUP_MEMBERS
+GROUP_MEMBERS = (96, 32, 4, 256)
+GROUP_RANK_CASES = {'group_ranks-1+300': ((1, 300), 4300), 'group_ranks-300+300': ((300, 300), 4310), 'group_ranks-0+257': ((0, 257), 4320)}
+
+
+def rank_case_inputs(name):
+    s = RANK_CASES[name]
+    return bn_input_ranks(s['rows'], s['c'], s['seed'])
+
+
+def half_rank_case_inputs(name):
+    rows, c, _, _, seed = HALF_RANK_CASES[name]
+    return bn_input_ranks(rows, c, seed, half=True)
+
+
+def pair_rank_case_inputs(name):
+    rows, c, _, seed = PAIR_RANK_CASES[name]
+    a, b = bn_input_ranks(rows, c, seed), bn_input_ranks(rows, c, seed + 50)
+    for d in b:
+        d['x'] = np.ascontiguousarray(d['x'][:, ::-1])         # another kind (and another spread) meets each column of a
+    return a, b
+
+
+def group_rank_case_inputs(name):
+    rows, seed = GROUP_RANK_CASES[name]
+    return [bn_input_ranks(rows, c, seed + j) for j, c in enumerate(GROUP_MEMBERS)]
+
+
+RANK_MISTAKES = ('mean_of_rank_means', 'pooled_within_variance', 'local_count_in_dx', 'local_sums_in_dx', 'unbiased_with_local_n',
+                 'count_is_world_times_local', 'param_grads_from_global_sums')
+
+
+def bn_ranks_emulate(inps, spec, mistake=None, half=False, pgs=1.0):
+    """bn_emulate / bn_emulate_h rank by rank: every rank's statistics as sequential fp64 sums down its columns, the packed sums
+    (sum x, sum x^2, n_r) added in rank order, the constants rounded once; the backward sums sequential in fp32 on every rank, widened
+    and added in rank order; fp32 element arithmetic, binary16 stores for `half`.  -> one dict per rank.  `mistake` (RANK_MISTAKES):
+        mean_of_rank_means            the mean is the unweighted mean of the ranks' means
+        pooled_within_variance        the variance is the row-weighted mean of the ranks' variances (the spread between ranks is lost)
+        local_count_in_dx             dx divides the global sums by the LOCAL row count
+        local_sums_in_dx              dx from this rank's sums and row count (a one-rank backward with the global constants)
+        unbiased_with_local_n         running_var's unbiased factor from the local row count
+        count_is_world_times_local    N = W * n_r
+        param_grads_from_global_sums  dbeta, dgamma from the all-reduced sums"""
+    f = np.float32
+    world = len(inps)
+    rows_n = [i['x'].shape[0] for i in inps]
+    p = inps[0]
+    c = p['x'].shape[1]
+    gamma, beta = f64(p['gamma']), f64(p['beta'])
+    packs = []
+    for i in inps:
+        xs = f64(i['x'])
+        packs.append((_seq64(xs), _seq64(xs * xs), float(xs.shape[0])))
+    s1, s2, cnt = np.zeros(c), np.zeros(c), 0.0
+    for a, b, k in packs:
+        s1, s2, cnt = s1 + a, s2 + b, cnt + k
+    rnd = (lambda a: _round_half(a)) if half else (lambda a: a)
+    mom = float(f(MOMENTUM))
+    fw = []
+    for r, i in enumerate(inps):
+        n = rows_n[r]
+        tot = float(world * n) if mistake == 'count_is_world_times_local' else cnt
+        with np.errstate(divide='ignore', invalid='ignore'):
+            m = s1 / tot
+            if mistake == 'mean_of_rank_means':
+                m = sum(a / k for a, _, k in packs if k) / sum(1 for _, _, k in packs if k)
+            var = np.maximum(s2 / tot - m * m, 0.0)
+            if mistake == 'pooled_within_variance':
+                var = sum(k * np.maximum(b / k - (a / k) ** 2, 0.0) for a, b, k in packs if k) / tot
+        nn = float(n) if mistake == 'unbiased_with_local_n' else tot
+        unb = var * nn / (nn - 1) if nn > 1 else var
+        got = {'running_mean': ((1 - mom) * f64(p['rm0']) + mom * m).astype(f),
+               'running_var': ((1 - mom) * f64(p['rv0']) + mom * unb).astype(f)}
+        inv = 1.0 / np.sqrt(var + float(f(EPS)))
+        mean32, inv32 = m.astype(f), inv.astype(f)
+        sc32, sh32 = (gamma * inv).astype(f), (beta - m * gamma * inv).astype(f)
+        got.update(mean=mean32, invstd=inv32, scale=sc32, shift=sh32)
+        x, dy = i['x'], i['dy']
+        v = (f64(x) * f64(sc32) + f64(sh32)).astype(f)                     # an fma: one rounding
+        if spec['res']:
+            v = v + i['res']
+        mask = None
+        if spec['relu']:
+            y = rnd(np.maximum(v, f(0)))
+            w = y if (spec['res'] or not half) else v
+            mask = w > 0
+            if half and not spec['res']:
+                got['mask'] = mask
+        else:
+            y = rnd(v)
+        got['y'] = y
+        g = dy * mask.astype(f) if mask is not None else dy
+        xh = (x - mean32) * inv32
+        fw.append((got, g, xh, _seq32(g), _seq32(g * xh), tot))
+        if spec['res']:
+            got['dres'] = rnd(g)
+    g1, g2 = np.zeros(c), np.zeros(c)
+    for _, _, _, a, b, _ in fw:
+        g1, g2 = g1 + f64(a), g2 + f64(b)
+    out = []
+    for r, (got, g, xh, sg, sgx, tot) in enumerate(fw):
+        n = rows_n[r]
+        a, b, over = g1, g2, tot
+        if mistake == 'local_sums_in_dx':
+            a, b, over = f64(sg), f64(sgx), float(n)
+        if mistake == 'local_count_in_dx':
+            over = float(n)
+        s = f(pgs)
+        if mistake == 'param_grads_from_global_sums':
+            got.update(dbeta=g1.astype(f) * s, dgamma=g2.astype(f) * s)
+        else:
+            got.update(dbeta=sg * s, dgamma=sgx * s)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            inv_n = f(1.0 / over) if over else f(0)
+        got['dx'] = rnd((p['gamma'] * got['invstd']) * (g - a.astype(f) * inv_n - xh * (b.astype(f) * inv_n)))
+        out.append(got)
+    return out
+
+
+def pair_ranks_emulate(a_inps, b_inps, relu):
+    """pair_emulate over ranks: two bn_ranks_emulate forwards, one fp32 add, the backward sums per rank, added in rank order."""
+    f = np.float32
+    plain = {'res': False, 'relu': False}
+    ea, eb = bn_ranks_emulate(a_inps, plain), bn_ranks_emulate(b_inps, plain)
+    world = len(a_inps)
+    total = float(sum(i['x'].shape[0] for i in a_inps))
+    gots, keep = [], []
+    for r in range(world):
+        y = ea[r]['y'] + eb[r]['y']
+        mask = (y > 0).astype(f) if relu else np.ones_like(y)
+        got = {'y': np.maximum(y, f(0)) if relu else y}
+        g = a_inps[r]['dy'] * mask
+        loc = {}
+        for s, inps, e in (('a', a_inps, ea), ('b', b_inps, eb)):
+            xh = (inps[r]['x'] - e[r]['mean']) * e[r]['invstd']
+            loc[s] = (xh, _seq32(g), _seq32(g * xh))
+            got.update({'dbeta_' + s: loc[s][1], 'dgamma_' + s: loc[s][2]})
+            got.update({k + '_' + s: e[r][k] for k in CONSTS})
+        gots.append(got)
+        keep.append((g, loc))
+    for s, inps, e in (('a', a_inps, ea), ('b', b_inps, eb)):
+        g1 = sum(f64(k[1][s][1]) for k in keep)
+        g2 = sum(f64(k[1][s][2]) for k in keep)
+        inv_n = f(1.0 / total)
+        for r in range(world):
+            g, loc = keep[r]
+            gots[r]['dx_' + s] = (inps[r]['gamma'] * e[r]['invstd']) * (g - g1.astype(f) * inv_n - loc[s][0] * (g2.astype(f) * inv_n))
+    return gots

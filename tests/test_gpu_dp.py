@@ -1,8 +1,11 @@
 """Data-parallel path on real kernels: two processes (gloo rendezvous, both on cuda:0 -- the test box has one GPU)
 run SelectionNet with SyncBN on disjoint scene shards; the result must equal one process on the union batch
 (SURVEY §8e parity rule), and the bucketed gradient all-reduce must deliver the rank mean."""
+import json
 import os
+import queue
 import socket
+import time
 
 import numpy as np
 import pytest
@@ -32,7 +35,10 @@ def _worker(rank, world, port, q, backend='gloo', env=None):
     torch.manual_seed(0)
     model = Model(cfg, *synth.scannet_tables(), device='cuda:%d' % local)      # parameters broadcast from rank 0
     mine = shard_scenes(8, rank, world)
-    batch = synth.collate([synth.make_scene(100 + s, target_voxels=2000, pts_per_m2=6000.0) for s in mine])
+    voxels = [2000] * len(mine)
+    if os.environ.get('B2M_TEST_SCENES'):          # unequal shards: "[[[scene, target_voxels], ...] of rank 0, ... of rank 1]"
+        mine, voxels = (list(t) for t in zip(*json.loads(os.environ['B2M_TEST_SCENES'])[rank]))
+    batch = synth.collate([synth.make_scene(100 + s, target_voxels=v, pts_per_m2=6000.0) for s, v in zip(mine, voxels)])
     model.train()
     losses, pred = model.compute_loss_detection(batch, 150)
     losses['optimization_loss'].backward()
@@ -43,7 +49,7 @@ def _worker(rank, world, port, q, backend='gloo', env=None):
     if F_.ipc_exchange is not None:
         F_.ipc_exchange.check()                  # no exchange gave up waiting for its peer
     q.put((rank, {'pred': {k: v.detach().cpu().numpy() for k, v in pred.items()}, 'grad': g.numpy(), 'named': named,
-                  'loss': float(losses['optimization_loss'].item()), 'scenes': mine,
+                  'loss': float(losses['optimization_loss'].item()), 'scenes': mine, 'voxels': voxels,
                   'rm': model.state_dict()['bn0.bn.running_mean'].cpu().numpy(),
                   'ipc': F_.collective_stats['ipc'], 'syncbn': F_.collective_stats['syncbn']}))
     dist.barrier()
@@ -64,17 +70,48 @@ def test_syncbn_and_gradient_mean_two_ranks():
     _two_rank_check('gloo')
 
 
+@pytest.mark.timeout(600)
+def test_syncbn_unequal_shards_two_ranks():
+    """Over the real transport (gloo), with shards that are NOT alike: rank 0 holds one small scene (some 150 voxels: single rows,
+    or none, on the deep levels and in the heads), rank 1 seven scenes of 2000.  The two ranks predict what one process predicts on
+    the union batch, within the project's tolerance (1e-3 of every head's largest value), end with the same running means and a
+    finite loss.  tests/test_gpu_syncbn_ranks.py holds every SyncBN operator to the fp64 rule for such ranks; this is the one run
+    through torch.distributed.  profiles/syncbn_ranks_rule.md has the measured errors."""
+    _two_rank_check('gloo', scenes=[[[0, 150]], [[s, 2000] for s in range(1, 8)]])
+
+
 def _run_two_ranks(backend, env=None):
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = _free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q, backend, env)) for r in range(2)]
-    for p in procs: p.start()
-    res = dict(q.get(timeout=500) for _ in range(2))
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
-    return res
+    try:
+        for p in procs: p.start()
+        res, deadline = {}, time.monotonic() + 500
+        while len(res) < 2:
+            try:
+                rank, out = q.get(timeout=1.0)
+                res[rank] = out
+            except queue.Empty:
+                # (a rank that raised leaves its peer waiting in a collective: say so at once, not after the time limit)
+                assert all(p.exitcode in (None, 0) for p in procs), 'a rank ended with %s' % ([p.exitcode for p in procs],)
+                if time.monotonic() > deadline:
+                    raise
+        for p in procs:
+            p.join(120)
+            assert p.exitcode == 0
+        return res
+    finally:
+        # whatever happened (a failed rendezvous, a rank that raised): no child is left holding the device
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+        for p in procs:
+            if p.pid is not None:
+                p.join(30)
+                if p.is_alive():
+                    p.kill()
+                    p.join(30)
 
 
 @pytest.mark.timeout(900)
@@ -114,8 +151,11 @@ def test_syncbn_execution_modes_agree_two_ranks():
                 assert e < 1e-3, (what, r, h, e)
 
 
-def _two_rank_check(backend, half=False, tol=1e-3):
-    res = _run_two_ranks(backend, {'B2M_TEST_HALF_TRAINING': '1'} if half else None)
+def _two_rank_check(backend, half=False, tol=1e-3, scenes=None):
+    env = {'B2M_TEST_HALF_TRAINING': '1'} if half else {}
+    if scenes is not None:
+        env['B2M_TEST_SCENES'] = json.dumps(scenes)
+    res = _run_two_ranks(backend, env or None)
     # single process on the union batch, same weights
     from box2mask_amd import synth
     from box2mask_amd.config import scannet_config
@@ -123,8 +163,8 @@ def _two_rank_check(backend, half=False, tol=1e-3):
     cfg = scannet_config(half_training=half)
     torch.manual_seed(0)
     model = Model(cfg, *synth.scannet_tables())
-    order = res[0]['scenes'] + res[1]['scenes']
-    batch = synth.collate([synth.make_scene(100 + s, target_voxels=2000, pts_per_m2=6000.0) for s in order])
+    order = list(zip(res[0]['scenes'] + res[1]['scenes'], res[0]['voxels'] + res[1]['voxels']))
+    batch = synth.collate([synth.make_scene(100 + s, target_voxels=v, pts_per_m2=6000.0) for s, v in order])
     model.train()
     losses, pred = model.compute_loss_detection(batch, 150)
     n0 = res[0]['pred']['mlp_offsets'].shape[0]

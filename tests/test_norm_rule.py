@@ -2,7 +2,10 @@
 empty-segment conventions against hand-computed cases, and its bounds against (a) an fp32 evaluation of the same formulas in an
 order unlike the kernels' -- they must not be too tight -- and (b) deliberate mistakes -- they must not be too loose -- on the very
 cases tests/test_gpu_norm.py runs; the same for the binary16 operator and the members of a SyncBN group (tests/test_gpu_norm_half.py),
-with the binary16 rounding conventions by hand.  No GPU.
+with the binary16 rounding conventions by hand.  The last sections: the rule for SyncBN ranks that hold different rows against float64
+torch on the concatenation, its bounds against an fp32 emulation of the ranks and against seven ways of combining the ranks'
+statistics wrongly (with a record of which of them a copied second rank cannot see), the replay harness of tests/_syncbn_ranks.py on
+a toy operator, and nn.batch_norm_group's choice between one packed exchange and many.  No GPU.
 """
 import functools
 
@@ -375,3 +378,189 @@ def test_group_members_are_the_syncbn_rule(name):
         assert not bad, (name, j, bad)
         bad, _ = R.bn_check('%s[%d]' % (name, j), inp, R.GROUP_SPEC, R.bn_emulate(inp, R.GROUP_SPEC, 'no_bessel'), quiet=True)
         assert bad and all(b.startswith('running_var') for b in bad), (name, j, bad)        # 2n rows in the unbiased factor
+
+
+# ================================================================== SyncBN over ranks that hold different rows
+@pytest.mark.parametrize('res,relu', [(0, 0), (1, 1), (0, 1)])
+def test_rank_rule_matches_torch_batchnorm_float64_on_the_concatenation(res, relu):
+    """The rule of the unequal ranks against float64 torch with autograd on X = [x_0; x_1; x_2]: y and dx by slices, the ranks'
+    parameter gradients by their sum."""
+    rows, c = (65, 1, 300), 32
+    inps = R.bn_input_ranks(rows, c, seed=11)
+    p = inps[0]
+    spec = {'res': bool(res), 'relu': bool(relu)}
+    assert [i['x'].shape for i in inps] == [(n, c) for n in rows]
+    means = np.array([i['x'].astype(np.float64).mean(0) for i in inps])
+    _, var = R.bn_stats(np.concatenate([i['x'] for i in inps]))
+    within = np.array([R.bn_stats(inps[r]['x'])[1] for r in (0, 2)]).max(0)
+    assert int((var > 5 * within + 1e-12).sum()) >= c // 8 and np.ptp(means, axis=0).max() > 0      # the spread between ranks dominates some columns
+    bn = torch.nn.BatchNorm1d(c, eps=R.EPS, momentum=float(np.float32(R.MOMENTUM))).double()
+    bn.eps = float(np.float32(R.EPS))
+    with torch.no_grad():
+        bn.weight.copy_(T(p['gamma'])); bn.bias.copy_(T(p['beta']))
+        bn.running_mean.copy_(T(p['rm0'])); bn.running_var.copy_(T(p['rv0']))
+    cat = lambda k: np.concatenate([i[k] for i in inps])
+    x, r = T(cat('x')).requires_grad_(True), T(cat('res')).requires_grad_(True)
+    pre = bn(x) + (r if res else 0)
+    y = torch.relu(pre) if relu else pre
+    (y * T(cat('dy'))).sum().backward()
+    rule = R.bn_ranks_rule(inps, spec)
+    lo = np.concatenate([[0], np.cumsum(rows)])
+    n_all = sum(rows)
+    for k, n in enumerate(rows):
+        sl = slice(lo[k], lo[k + 1])
+        close(rule[k]['y'], y.detach().numpy()[sl], 'y')
+        # (dx relative to the tensor's column maxima, not the slice's: a one-row slice may hold a cancelled value)
+        assert np.all(np.abs(rule[k]['dx'] - x.grad.numpy()[sl]) <= 1e-9 * np.abs(x.grad.numpy()).max(0)), k
+        close(rule[k]['running_mean'], bn.running_mean.numpy(), 'running_mean')
+        close(rule[k]['running_var'], bn.running_var.numpy(), 'running_var')
+        if res:
+            close(rule[k]['dres'], r.grad.numpy()[sl], 'dres')
+    close(sum(d['dgamma'] for d in rule), bn.weight.grad.numpy(), 'sum of dgamma_r', rel=1e-9 * n_all)
+    close(sum(d['dbeta'] for d in rule), bn.bias.grad.numpy(), 'sum of dbeta_r', rel=1e-9 * n_all)
+    # the check holds what the rule says: the rule's own values pass it with error 0
+    bad, _ = R.bn_ranks_check('rule', inps, spec, rule, [64, 64, 64], quiet=True)
+    assert not bad, bad
+
+
+def _rank_emulation(name):
+    if name in R.RANK_CASES:
+        s = R.RANK_CASES[name]
+        inps = R.rank_case_inputs(name)
+        return R.bn_ranks_check(name, inps, s, R.bn_ranks_emulate(inps, s), R.rank_chains(s['rows'], s['small_rows']))
+    if name in R.HALF_RANK_CASES:
+        rows, c, res, relu, _ = R.HALF_RANK_CASES[name]
+        inps, spec = R.half_rank_case_inputs(name), {'res': res, 'relu': relu}
+        pgs = 2.0 ** -10
+        return R.bn_ranks_check_half(name, inps, spec, R.bn_ranks_emulate(inps, spec, half=True, pgs=pgs), pgs=pgs)
+    if name in R.PAIR_RANK_CASES:
+        a, b = R.pair_rank_case_inputs(name)
+        relu = R.PAIR_RANK_CASES[name][2]
+        return R.pair_ranks_check(name, a, b, relu, R.pair_ranks_emulate(a, b, relu))
+    members = R.group_rank_case_inputs(name)
+    plain = {'res': False, 'relu': False}
+    return R.group_ranks_check(name, members, [R.bn_ranks_emulate(inps, plain) for inps in members]), 0.0
+
+
+@pytest.mark.parametrize('name', list(R.RANK_CASES) + list(R.HALF_RANK_CASES) + list(R.PAIR_RANK_CASES) + list(R.GROUP_RANK_CASES))
+def test_rank_fp32_emulation_passes_and_few_elements_are_borderline(name):
+    bad, share = _rank_emulation(name)
+    assert not bad, (name, bad)
+    assert share <= 1e-3, (name, share)
+
+
+def test_rank_cases_hold_their_edges():
+    rows = {s['rows'] for s in R.RANK_CASES.values()}
+    assert {(300, 300), (1, 300), (2048, 2049), (256, 257), (0, 257), (1, 1), (65, 1, 4033)} <= rows
+    assert {s['c'] for s in R.RANK_CASES.values()} == {4, 32, 96, 256} and 512 in {v[1] for v in R.HALF_RANK_CASES.values()}
+    assert {(s['res'], s['relu']) for s in R.RANK_CASES.values()} == {(False, False), (True, True), (False, True)}
+    for name, s in R.RANK_CASES.items():
+        chains = R.rank_chains(s['rows'], s['small_rows'])
+        if s['rows'] in ((2048, 2049), (256, 257)):
+            assert chains == [1, 64], name                                                  # the two paths meet in one exchange
+    assert any(s.get('tiles') is not None for s in R.RANK_CASES.values())
+
+
+# mistake -> the unequal case that has to catch it
+RANK_MISTAKE_CASE = {'mean_of_rank_means': 'ranks-1+300-c96-res0-relu1', 'pooled_within_variance': 'ranks-300+300-c32-res1-relu1',
+                     'local_count_in_dx': 'ranks-1+300-c96-res0-relu1', 'local_sums_in_dx': 'ranks-300+300-c32-res1-relu1',
+                     'unbiased_with_local_n': 'ranks-1+300-c96-res0-relu1', 'count_is_world_times_local': 'ranks-1+300-c96-res0-relu1',
+                     'param_grads_from_global_sums': 'ranks-300+300-c32-res1-relu1'}
+# ... and whether the form every SyncBN test used before (the second rank a copy of the first: count_factor = 2) sees it
+BLIND_WITH_A_COPIED_RANK = {'mean_of_rank_means', 'pooled_within_variance', 'local_sums_in_dx', 'count_is_world_times_local'}
+
+
+def _copied_rank_form(mistake):
+    """The mistake on two ranks that hold the SAME rows, rank 0 held to the rule on [x; x] as the one-process SyncBN tests do."""
+    spec = dict(R.BN_CASES['sync-n257-c32-res0-relu1'])
+    inp = R.bn_case_input('sync-n257-c32-res0-relu1')
+    got = R.bn_ranks_emulate([inp, inp], spec, mistake)[0]
+    bad, _ = R.bn_check('copied rank, ' + str(mistake), inp, spec, got, quiet=True)
+    return bad
+
+
+@pytest.mark.parametrize('mistake', R.RANK_MISTAKES)
+def test_a_deliberate_rank_mistake_fails_its_unequal_case(mistake):
+    name = RANK_MISTAKE_CASE[mistake]
+    s, inps = R.RANK_CASES[name], R.rank_case_inputs(name)
+    assert len(set(s['rows'])) > 1 or not np.array_equal(inps[0]['x'], inps[1]['x'])
+    bad, _ = R.bn_ranks_check(name, inps, s, R.bn_ranks_emulate(inps, s, mistake), R.rank_chains(s['rows'], s['small_rows']), quiet=True)
+    copied = _copied_rank_form(mistake)
+    print('%-30s %-32s fails: %-60s copied rank: %s' % (mistake, name, sorted({b.split('[')[0].split(':')[0] for b in bad}),
+                                                        'seen' if copied else 'BLIND'))
+    assert bad, 'the unequal ranks of %s let the mistake %s pass' % (name, mistake)
+    assert (not copied) == (mistake in BLIND_WITH_A_COPIED_RANK), (mistake, copied)
+
+
+def test_the_copied_rank_form_passes_without_a_mistake():
+    assert not _copied_rank_form(None)
+
+
+# ------------------------------------------------------------------ the replay harness on a toy operator
+def _toy_rank(data, extra=None):
+    """Two exchanges in a chain: (sum v, n) -> mean, then sum (v - mean)^2 -> variance; `extra`: a rank that issues one exchange
+    more, or one of another size."""
+    def run(r, all_reduce):
+        v = data[r]
+        first = np.array([v.sum(), float(len(v))])
+        all_reduce(first)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            mean = first[0] / first[1]
+            second = np.array([((v - mean) ** 2).sum()] + ([0.0] if extra == ('size', r) else []))
+            all_reduce(second)
+            if extra == ('more', r):
+                all_reduce(np.zeros(1))
+            return {'mean': np.array([mean]), 'var': np.array([second[0] / first[1]])}
+    return run
+
+
+def test_replay_converges_in_three_passes_and_reports_a_sequence_mismatch():
+    import _syncbn_ranks as S
+    rng = np.random.default_rng(5)
+    data = [rng.standard_normal(n) + 3.0 * r for r, n in enumerate((7, 1, 0, 40))]
+    out, seq = S.replay(4, _toy_rank(data), 3)
+    allv = np.concatenate(data)
+    assert seq == [(2, np.dtype('float64')), (1, np.dtype('float64'))]
+    for o in out:                                                                             # every rank, the one without rows too
+        assert abs(o['mean'][0] - allv.mean()) <= 1e-14 * abs(allv).max() and abs(o['var'][0] - allv.var()) <= 1e-13 * allv.var()
+        assert o['var'][0] == out[0]['var'][0]
+    with pytest.raises(AssertionError, match='too few'):                                      # two passes: the second sum is not yet right
+        S.replay(4, _toy_rank(data), 2)
+    for kind in ('more', 'size'):
+        with pytest.raises(AssertionError, match=r'rank 0 issued \[\(2, float64\), \(1, float64\)\], rank 2 issued \[\(2, float64\), ') as e:
+            S.replay(4, _toy_rank(data, (kind, 2)), 3)
+        assert 'wait for each other' in str(e.value)
+
+
+# ------------------------------------------------------------------ grouped or layer by layer: every rank decides alike
+@pytest.mark.parametrize('switch', ['1', '0'])
+def test_batch_norm_group_decides_alike_for_one_row_and_for_many(switch, monkeypatch):
+    """nn.batch_norm_group chooses between one packed exchange per direction and 2m small ones: a choice that looked at this
+    rank's row count would set a rank with one pooled row (or none) against its peers.  The operator is a stub: no kernel runs."""
+    from box2mask_amd import functional as F_, nn as ME
+    monkeypatch.setenv('B2M_BN_GROUP', switch)
+    marker = object()
+    monkeypatch.setattr(F_, '_sync_group', lambda: marker)
+    grouped, single = [], []
+    monkeypatch.setattr(F_, 'batch_norm_group', lambda members, group: (grouped.append((len(members), group)), [m[0] for m in members])[1])
+    monkeypatch.setattr(F_, 'batch_norm', lambda feats, *a, **k: (single.append(feats.shape[0]), feats)[1])
+    decisions = {}
+    for n in (0, 1, 300):
+        norms = [ME.MinkowskiBatchNorm(c) for c in R.GROUP_MEMBERS]
+        for nm in norms:
+            nm.sync = True
+            nm.train()
+        pooled = ME.PooledTensor(torch.zeros(n, 8))
+        ts = [ME.PooledTensor(torch.ones(n, c), pooled.serial) for c in R.GROUP_MEMBERS]
+        del grouped[:], single[:]
+        out = ME.batch_norm_group(norms, ts)
+        assert [tuple(o.F.shape) for o in out] == [(n, c) for c in R.GROUP_MEMBERS]
+        decisions[n] = (list(grouped), len(single))
+        assert all(int(nm.bn.num_batches_tracked) == 1 for nm in norms)
+    want = ([(len(R.GROUP_MEMBERS), marker)], 0) if switch == '1' else ([], len(R.GROUP_MEMBERS))
+    assert decisions == {0: want, 1: want, 300: want}, decisions
+    # one process (no group): one row is torch's own complaint, as before
+    monkeypatch.setattr(F_, '_sync_group', lambda: None)
+    nm = ME.MinkowskiBatchNorm(4).train()
+    with pytest.raises(ValueError):
+        ME.batch_norm_group([nm, nm], [ME.PooledTensor(torch.ones(1, 4))] * 2)
