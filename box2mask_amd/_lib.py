@@ -108,6 +108,7 @@ PROTOTYPES = {
     'b2m_dbscan': [P, I64, I32, F64, I32, P, P, P, P],
     'b2m_paint_proposals': [P, I64, I32, P, I64, I32, F64, I32, P, P, P, P, P],
     'b2m_joint_hist': [P, P, I64, I32, I32, P, P],
+    'b2m_s3dis_prefix_tail': [P, P, I32, P, P, I64, P, I32, I32, I32, P, P, P, I32, P, I64, P, P, P, I32, P, P, P],
     # include/b2m_prepare.h
     'b2m_vox_shift': [P, I64, P, P, P],
     'b2m_unique_insert_async': [P, I64, P, I64, P, P, P, P],
@@ -154,6 +155,7 @@ PLAIN = {'b2m_last_error': (C.c_char_p, []), 'b2m_version': (C.c_int, []), 'b2m_
          'b2m_rulebook_cnt_size': (C.c_int64, [I32, I64]),
          'b2m_radix_argsort_scratch': (C.c_int64, [I64]),
          'b2m_dbscan_workspace': (C.c_int64, [I64]),
+         'b2m_s3dis_prefix_tail_workspace': (C.c_int64, [I32, I32, I32, I32]),
          'b2m_nn_workspace': (C.c_int64, [I64]),
          'b2m_xchg_size': (C.c_int64, []), 'b2m_xchg_max_doubles': (C.c_int32, []), 'b2m_xchg_max_ranks': (C.c_int32, []),
          'b2m_xchg_alloc': (C.c_int, [C.POINTER(C.c_void_p), P]), 'b2m_xchg_open': (C.c_int, [P, C.POINTER(C.c_void_p)]),

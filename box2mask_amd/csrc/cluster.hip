@@ -466,3 +466,215 @@ extern "C" int b2m_joint_hist(const int32_t* a, const int32_t* b, int64_t n, int
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }
+
+// ------------------------------------------------------------------ S3DIS threshold sweep: every score prefix of one stage
+// (include/b2m.h, b2m_s3dis_prefix_tail).  A (setting x point-chunk) grid; the tables of a setting are privatised in LDS when they
+// fit (one global integer add per touched cell and workgroup), else the adds go to global memory.  Integer adds and plain stores
+// of one value only: the tables do not depend on the order of the atomics.
+#define PT_THREADS 256
+#define PT_PER_BLOCK (PT_THREADS * 16)
+#define PT_LDS 8192
+#define PT_CLASSES 13
+struct PtPrefix { int32_t k[B2M_SWEEP_MAX_TH]; };
+struct PtLayout { int64_t present, maxid, pair, size, cls, inter, total; };
+static PtLayout pt_layout(int64_t k_rows, int64_t n_set, int64_t n_inst, int64_t n_gt) {
+    PtLayout L;
+    int64_t at = 0;
+    auto take = [&](int64_t ints) { const int64_t p = at; at += (ints + 63) / 64 * 64; return p; };
+    L.present = take(k_rows > 0 ? k_rows : 1);
+    L.maxid = take(n_set);
+    L.pair = take(n_set * n_inst * PT_CLASSES);
+    L.size = take(n_set * n_inst);
+    L.cls = take(n_set * n_inst * PT_CLASSES);
+    L.inter = take(n_set * n_inst * (n_gt > 0 ? n_gt : 1));
+    L.total = at;
+    return L;
+}
+static bool pt_sizes_ok(int64_t k_rows, int64_t n_set, int64_t n_inst, int64_t n_gt) {
+    return k_rows >= 0 && k_rows < (1ll << 31) && n_set >= 1 && n_set <= B2M_SWEEP_MAX_TH && n_inst >= 1 && n_inst < (1ll << 31) &&
+           n_gt >= 0 && n_gt < (1ll << 31) && n_set * n_inst <= B2M_JOINT_HIST_MAX &&
+           n_set * n_inst * (n_gt > PT_CLASSES ? n_gt : PT_CLASSES) <= B2M_JOINT_HIST_MAX;
+}
+extern "C" int64_t b2m_s3dis_prefix_tail_workspace(int32_t k_rows, int32_t n_set, int32_t n_inst, int32_t n_gt) {
+    if (!pt_sizes_ok(k_rows, n_set, n_inst, n_gt)) return -1;
+    return pt_layout(k_rows, n_set, n_inst, n_gt).total * (int64_t)sizeof(int32_t);
+}
+
+// the label of sampled point p in a setting before the small pairs go: evaluation.py:192-199 restricted to the owners below k_s
+__device__ __forceinline__ void pt_label(const int32_t* __restrict__ owner, const int32_t* __restrict__ prop_sem,
+                                         const int32_t* __restrict__ bg, const int32_t* __restrict__ sem, int64_t p, int k_s,
+                                         int k_rows, int maxid, int n_inst, int& inst, int& cls) {
+    const int o = owner[p];
+    const bool painted = o >= 0 && o < k_s && o < k_rows;
+    inst = painted ? o + 1 : -1;
+    cls = painted ? prop_sem[o] : sem[p];
+    const int b = bg[p];
+    if (b > 0 && (int64_t)b + maxid > 0) inst = (int64_t)b + maxid < n_inst ? b + maxid : n_inst;
+    if (inst >= n_inst) inst = -1;
+}
+
+__global__ __launch_bounds__(PT_THREADS) void pt_present_kernel(const int32_t* __restrict__ owner, int64_t n, int k_rows,
+                                                                int32_t* __restrict__ present) {
+    for (int64_t p = (int64_t)blockIdx.x * PT_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * PT_THREADS) {
+        const int o = owner[p];
+        if (o >= 0 && o < k_rows) present[o] = 1;   // (every writer stores the same value)
+    }
+}
+// maxid[s] = 1 + the largest owner below k[s] that owns a point, or -1: np.max(pred_instances) of the prefix (evaluation.py:197)
+__global__ __launch_bounds__(64) void pt_maxid_kernel(const int32_t* __restrict__ present, PtPrefix pre, int n_set,
+                                                      int32_t* __restrict__ maxid) {
+    const int s = threadIdx.x;
+    if (s >= n_set) return;
+    int m = -1;
+    for (int o = pre.k[s] - 1; o >= 0; --o)
+        if (present[o]) { m = o + 1; break; }
+    maxid[s] = m;
+}
+
+// table[key] += 1 for every lane with `on`, ONE add per wave and distinct key (the points of a room come in long runs of one
+// instance: without this the 64 lanes of a wave queue on one cell).  Every lane of the wave must call it.
+__device__ __forceinline__ void pt_wave_add(int32_t* table, int key, bool on) {
+    uint64_t todo = __ballot(on);
+    while (todo) {                                  // (uniform over the wave)
+        const int leader = __builtin_ctzll(todo);
+        const int k = __shfl(key, leader);
+        const uint64_t same = __ballot(on && key == k);
+        if (lane_id() == leader) atomicAdd(&table[k], __builtin_popcountll(same));
+        todo &= ~same;
+    }
+}
+
+// blockIdx.y = setting.  PASS 0: (instance, class) counts over the sampled points.  PASS 1: sizes, class votes and ground-truth
+// intersections over the evaluation points, after the pairs under min_points lost their points (evaluation.py:200-222).
+template <int PASS, bool LDS>
+__global__ __launch_bounds__(PT_THREADS) void pt_count_kernel(const int32_t* __restrict__ owner, const int32_t* __restrict__ prop_sem,
+                                                              const int32_t* __restrict__ bg, const int32_t* __restrict__ sem,
+                                                              int64_t n, PtPrefix pre, int k_rows, int n_inst, int min_points,
+                                                              const int32_t* __restrict__ gi, int n_gt,
+                                                              const int64_t* __restrict__ index, int64_t n_eval,
+                                                              const int32_t* __restrict__ maxid, int32_t* __restrict__ pair,
+                                                              int32_t* __restrict__ size, int32_t* __restrict__ cls_tab,
+                                                              int32_t* __restrict__ inter, int label_setting, int32_t* __restrict__ inst_out,
+                                                              int32_t* __restrict__ sem_out) {
+    __shared__ int h[LDS ? PT_LDS : 1];
+    const int s = blockIdx.y;
+    const int k_s = pre.k[s], mx = maxid[s];
+    const int gw = n_gt > 0 ? n_gt : 1;
+    // LDS image of the setting's tables: PASS 0 pair[n_inst][13]; PASS 1 size[n_inst] | cls[n_inst][13] | inter[n_inst][gw]
+    const int cells = PASS == 0 ? n_inst * PT_CLASSES : n_inst * (1 + PT_CLASSES + gw);
+    const int o_cls = n_inst, o_inter = n_inst * (1 + PT_CLASSES);
+    const int32_t* pair_s = pair + (int64_t)s * n_inst * PT_CLASSES;
+    if (LDS) {
+        for (int c = threadIdx.x; c < cells; c += PT_THREADS) h[c] = 0;
+        __syncthreads();
+    }
+    const int64_t total = PASS == 0 ? n : n_eval;
+    // the tables of this setting, in LDS or in global memory; every wave walks the loop as a whole (pt_wave_add ballots)
+    int32_t* t_pair = LDS ? h : pair + (int64_t)s * n_inst * PT_CLASSES;
+    int32_t* t_size = LDS ? h : size + (int64_t)s * n_inst;
+    int32_t* t_cls = LDS ? h + o_cls : cls_tab + (int64_t)s * n_inst * PT_CLASSES;
+    int32_t* t_inter = LDS ? h + o_inter : inter + (int64_t)s * n_inst * gw;
+    for (int64_t q0 = (int64_t)blockIdx.x * PT_THREADS; q0 < total; q0 += (int64_t)gridDim.x * PT_THREADS) {
+        const int64_t q = q0 + threadIdx.x;
+        const bool live = q < total;
+        int64_t p = q;
+        if (PASS == 1 && index && live) p = index[q];
+        int inst = -1, c = -1;
+        const bool inside = live && p >= 0 && p < n;
+        if (inside) pt_label(owner, prop_sem, bg, sem, p, k_s, k_rows, mx, n_inst, inst, c);
+        const bool cok = c >= 0 && c < PT_CLASSES;
+        if (PASS == 0) {
+            pt_wave_add(t_pair, inst * PT_CLASSES + c, inst >= 0 && cok);
+            continue;                               // (uniform over the workgroup: PASS is a template argument)
+        }
+        if (inst >= 0 && cok && pair_s[(int64_t)inst * PT_CLASSES + c] < min_points) inst = -1;
+        const int g = live ? gi[q] : -1;
+        const bool gok = g >= 0 && g < n_gt;
+        if (live && s == label_setting) {
+            if (inst_out) inst_out[q] = inst;
+            if (sem_out) sem_out[q] = inside ? c : -1;
+        }
+        pt_wave_add(t_size, inst, inst >= 0);
+        pt_wave_add(t_cls, inst * PT_CLASSES + c, inst >= 0 && cok);
+        pt_wave_add(t_inter, inst * gw + g, inst >= 0 && gok);
+    }
+    if (!LDS) return;
+    __syncthreads();
+    for (int c = threadIdx.x; c < cells; c += PT_THREADS) {
+        const int v = h[c];
+        if (!v) continue;
+        if (PASS == 0) atomicAdd(&pair[(int64_t)s * n_inst * PT_CLASSES + c], v);
+        else if (c < o_cls) atomicAdd(&size[(int64_t)s * n_inst + c], v);
+        else if (c < o_inter) atomicAdd(&cls_tab[(int64_t)s * n_inst * PT_CLASSES + (c - o_cls)], v);
+        else atomicAdd(&inter[(int64_t)s * n_inst * gw + (c - o_inter)], v);
+    }
+}
+
+// one thread per (setting, instance): class = most frequent rewritten class (lowest on ties, scipy.stats.mode), true positive iff a
+// ground-truth instance of that class has inter / union >= 0.5, i.e. 3 * inter >= |P| + |G| (s3dis_util.py:280-296)
+__global__ __launch_bounds__(PT_THREADS) void pt_score_kernel(const int32_t* __restrict__ size, const int32_t* __restrict__ cls_tab,
+                                                              const int32_t* __restrict__ inter, const int32_t* __restrict__ gsize,
+                                                              const int32_t* __restrict__ gt_class, int n_set, int n_inst, int n_gt,
+                                                              int32_t* __restrict__ tp, int32_t* __restrict__ fp) {
+    const int64_t t = (int64_t)blockIdx.x * PT_THREADS + threadIdx.x;
+    if (t >= (int64_t)n_set * n_inst) return;
+    const int64_t sz = size[t];
+    if (sz <= 0) return;
+    const int s = (int)(t / n_inst);
+    int best = 0, bc = cls_tab[t * PT_CLASSES];
+    for (int c = 1; c < PT_CLASSES; ++c) {
+        const int v = cls_tab[t * PT_CLASSES + c];
+        if (v > bc) { bc = v; best = c; }
+    }
+    const int gw = n_gt > 0 ? n_gt : 1;
+    bool hit = false;
+    for (int g = 0; g < n_gt && !hit; ++g)
+        hit = gt_class[g] == best && 3 * (int64_t)inter[t * gw + g] >= sz + (int64_t)gsize[g];
+    atomicAdd(hit ? &tp[s * PT_CLASSES + best] : &fp[s * PT_CLASSES + best], 1);
+}
+
+extern "C" int b2m_s3dis_prefix_tail(const int32_t* owner, const int32_t* prop_sem, int32_t k_rows, const int32_t* bg,
+                                     const int32_t* sem, int64_t n, const int32_t* k_host, int32_t n_set, int32_t n_inst,
+                                     int32_t min_points, const int32_t* gi, const int32_t* gt_class, const int32_t* gt_size,
+                                     int32_t n_gt, const int64_t* index, int64_t n_eval, void* workspace, int32_t* tp, int32_t* fp,
+                                     int32_t label_setting, int32_t* inst_out, int32_t* sem_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(n_set >= 1 && n_set <= B2M_SWEEP_MAX_TH, "n_set must be 1 ... B2M_SWEEP_MAX_TH");
+    B2M_CHECK_ARG(k_host, "NULL k_host");
+    B2M_CHECK_ARG(k_rows >= 0 && n >= 0 && n < (1ll << 31) && n_eval >= 0 && n_eval < (1ll << 31) && n_inst >= 1 && n_gt >= 0,
+                  "bad sizes");
+    PtPrefix pre;
+    for (int s = 0; s < n_set; ++s) {
+        B2M_CHECK_ARG(k_host[s] >= 0, "negative prefix length");
+        B2M_CHECK_ARG(s == 0 || k_host[s] <= k_host[s - 1], "the prefix lengths must not increase");
+        pre.k[s] = k_host[s];
+    }
+    for (int s = n_set; s < B2M_SWEEP_MAX_TH; ++s) pre.k[s] = 0;
+    B2M_CHECK_ARG(k_host[0] <= k_rows, "k[0] exceeds the number of proposal rows");
+    B2M_CHECK_ARG(pt_sizes_ok(k_rows, n_set, n_inst, n_gt), "tables of more than B2M_JOINT_HIST_MAX entries");
+    B2M_CHECK_ARG(label_setting >= -1 && label_setting < n_set, "label_setting must be -1 or a setting");
+    if (n == 0 || n_eval == 0) return B2M_OK;       // nothing to score: no launch, nothing written
+    B2M_CHECK_ARG(owner && bg && sem && gi && workspace && tp && fp, "NULL argument");
+    B2M_CHECK_ARG(k_rows == 0 || prop_sem, "NULL prop_sem");
+    B2M_CHECK_ARG(n_gt == 0 || (gt_class && gt_size), "NULL gt_class / gt_size");
+    const PtLayout L = pt_layout(k_rows, n_set, n_inst, n_gt);
+    int32_t* w = (int32_t*)workspace;
+    B2M_HIP(hipMemsetAsync(w, 0, (size_t)L.total * sizeof(int32_t), st));
+    auto grid_x = [](int64_t rows) { const int64_t b = cdiv64(rows, PT_PER_BLOCK); return (unsigned)(b > 1024 ? 1024 : b); };
+    pt_present_kernel<<<grid_x(n), PT_THREADS, 0, st>>>(owner, n, k_rows, w + L.present);
+    pt_maxid_kernel<<<1, 64, 0, st>>>(w + L.present, pre, n_set, w + L.maxid);
+    const int gw = n_gt > 0 ? n_gt : 1;
+    const bool lds0 = (int64_t)n_inst * PT_CLASSES <= PT_LDS, lds1 = (int64_t)n_inst * (1 + PT_CLASSES + gw) <= PT_LDS;
+#define PT_ARGS owner, prop_sem, bg, sem, n, pre, k_rows, n_inst, min_points, gi, n_gt, index, n_eval, w + L.maxid, w + L.pair, \
+                w + L.size, w + L.cls, w + L.inter, label_setting, inst_out, sem_out
+    const dim3 g0(grid_x(n), (unsigned)n_set), g1(grid_x(n_eval), (unsigned)n_set);
+    if (lds0) pt_count_kernel<0, true><<<g0, PT_THREADS, 0, st>>>(PT_ARGS);
+    else pt_count_kernel<0, false><<<g0, PT_THREADS, 0, st>>>(PT_ARGS);
+    if (lds1) pt_count_kernel<1, true><<<g1, PT_THREADS, 0, st>>>(PT_ARGS);
+    else pt_count_kernel<1, false><<<g1, PT_THREADS, 0, st>>>(PT_ARGS);
+#undef PT_ARGS
+    pt_score_kernel<<<(unsigned)cdiv64((int64_t)n_set * n_inst, PT_THREADS), PT_THREADS, 0, st>>>(
+        w + L.size, w + L.cls, w + L.inter, gt_size, gt_class, n_set, n_inst, n_gt, tp, fp);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}

@@ -275,6 +275,23 @@ def s3dis_eval_from_counts(rooms, details=False):
     return out + (extra,)
 
 
+def instance_counts(rooms):
+    """The integers behind precision and recall (s3dis_util.py:273-299) over the per-room tables of ``s3dis_counts``: (tp (13),
+    fp (13), total_gt (13)) int64.  A predicted instance is a true positive when a ground-truth instance of its class has
+    inter / union >= 0.5, i.e. 3 * inter >= |P| + |G| -- the same decision as the float division for counts below 2^31."""
+    tp, fp, total = (np.zeros(NUM_CLASSES, np.int64) for _ in range(3))
+    for room in rooms:
+        inter = np.asarray(room['inter'], np.int64)
+        psize, gsize = np.asarray(room['pred_size'], np.int64), np.asarray(room['gt_size'], np.int64)
+        pcls, gcls = np.asarray(room['pred_class']), np.asarray(room['gt_class'])
+        total += np.bincount(gcls, minlength=NUM_CLASSES)[:NUM_CLASSES]
+        for p, c in enumerate(pcls):
+            same = gcls == c
+            hit = bool((3 * inter[p][same] >= psize[p] + gsize[same]).any())
+            (tp if hit else fp)[c] += 1
+    return tp, fp, total
+
+
 def s3dis_eval(pred_labels, gt_labels, details=False):
     """s3dis_util.s3dis_eval(pred_labels, gt_labels): lists of {'semantics', 'instances'} per room (arrays or tensors)."""
     assert len(pred_labels) == len(gt_labels)

@@ -32,12 +32,18 @@ scored with differs:
                                                                                         scene and stage: 24 hull stages, not 600;
   * rows under 50 points are skipped AFTER the mask NMS (evaluation.py:280)          -> ``detection_records`` gates what ``compose`` kept.
 
+The S3DIS flow (per-voxel semantics head, no mask NMS; evaluation.py:124-231) is the third: ``s3dis_param_search`` scores mPrec / mRec.
+There the wall DBSCAN depends on no threshold (once per room), the greedy merge of the proposals is prefix-closed (one
+``b2m_paint_proposals`` per (cluster_th, mask_bin_th) over the rows of the smallest score_th) and ``b2m_s3dis_prefix_tail`` scores every
+score prefix of a stage at once; profiles/s3dis_sweep_rule.md has the rule.
+
 ``detection_tables`` / ``detection_records`` / ``arkit_param_search``; matching and VOC AP are the unchanged ``eval_detection.eval_det``.  ``compose`` and the matching are host logic like ``assign_from_counts``; every kernel stage is HIP.
 With ``matching='device'`` the matching, the curves and the AP run on the device as well (eval_match.py): the stage results are
 matched where they lie and nothing but an entry count per stage comes to the host.
 """
 from __future__ import annotations
 
+import contextlib
 import itertools
 import warnings
 
@@ -122,8 +128,9 @@ def records(tables, ci, si, bi, mi):
 def _scene_inputs(net, batch, pred, cfg, dev):
     """Stage 0 of ``SelectionNet.detection2mask`` in the ScanNet flow: boxes of the foreground votes, their slots, the voxel labels."""
     if net.requires_voxel_outputs:
-        raise ValueError('the threshold sweep covers the ScanNet flow only (segment-level votes, mask NMS): a network with a '
-                         'per-voxel semantics head (requires_voxel_outputs) has no mask NMS to sweep')
+        raise ValueError('this threshold sweep covers the ScanNet flow only (segment-level votes, mask NMS): a network with a '
+                         'per-voxel semantics head (requires_voxel_outputs) has no mask NMS to sweep -- its thresholds are swept '
+                         'with the S3DIS metric by param_search.s3dis_param_search')
     pdev = pred[cfg.mlp_offsets].device
     pred_bbs = to_bbs_min_max(batch['input_location'].to(pdev), pred[cfg.mlp_offsets], pred[cfg.mlp_bounds],
                               torch.nn.Sigmoid()(pred[cfg.mlp_bb_scores]))
@@ -614,4 +621,238 @@ def _search_device(model, batches, gt_ids_by_scene, grid, per_class, shape, sett
     out = dict(ap=ap, best=best, best_ths=grid.eval_ths(*best), n_evaluated=len(settings))
     if per_class:
         out['ap_tables'] = table.reshape(shape + (len(eval_metric.CLASS_LABELS), len(eval_metric.OVERLAPS)))[..., None, :, :].copy()
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------- S3DIS mPrec / mRec
+class S3DISSweepResult(dict):
+    """The dict ``s3dis_param_search`` returns, with ``best``."""
+
+    def best(self, criterion='f1'):
+        """The setting with the largest harmonic mean of mPrec and mRec, as a ``cfg.eval_ths`` list (mask_nms_th = the grid's
+        first value: it has no effect in this flow).  A NaN counts as -inf; ties go to the first setting in grid order.  The
+        reference's search only prints the metrics of every job; this choice is this project's own."""
+        if criterion != 'f1':
+            raise ValueError("criterion: only 'f1' (the harmonic mean of mPrec and mRec) is defined, got %r" % (criterion,))
+        p, r = self['mprec'], self['mrec']
+        with np.errstate(all='ignore'):
+            f1 = 2.0 * p * r / (p + r)
+        f1 = np.where(np.isnan(f1), -np.inf, f1)
+        ci, si, bi = (int(v) for v in np.unravel_index(int(np.argmax(f1.reshape(-1))), f1.shape))     # argmax: the first of equals
+        return self['grid'].eval_ths(ci, si, bi, 0)
+
+
+def _s3dis_room(net, batch, pred, cfg, dev):
+    """Stage 0 of ``SelectionNet.detection2mask`` in the S3DIS flow (detection_net.py:398-415) for a batch of ONE room: the boxes
+    of the segments whose voxels vote a foreground class, their slots, and the predicted class of every point."""
+    from .eval_s3dis import NUM_CLASSES
+    if not net.requires_voxel_outputs or cfg.mlp_per_vox_semantics not in cfg.network_heads:
+        raise ValueError('s3dis_param_search needs the per-voxel semantics head (%s); the ScanNet / ARKitScenes flows are swept by '
+                         'scannet_param_search / arkit_param_search' % cfg.mlp_per_vox_semantics)
+    if len(batch['scene']) != 1:
+        raise ValueError('S3DIS is evaluated with batch size 1 (evaluation.py:131)')
+    pdev = pred[cfg.mlp_offsets].device
+    pred_bbs = to_bbs_min_max(batch['input_location'].to(pdev), pred[cfg.mlp_offsets], pred[cfg.mlp_bounds],
+                              torch.nn.Sigmoid()(pred[cfg.mlp_bb_scores]))
+    sem_vox = torch.argmax(torch.as_tensor(pred[cfg.mlp_per_vox_semantics]), 1).to(dev).int().contiguous()
+    if cfg.do_segment_pooling:
+        s2v = torch.as_tensor(batch['seg2vox'][0]).long().to(dev).contiguous()
+    else:
+        s2v = torch.arange(sem_vox.shape[0], dtype=torch.long, device=dev)
+    n_vox = int(s2v.shape[0])
+    if sem_vox.shape[0] != n_vox:
+        raise ValueError('%d per-voxel predictions for %d voxels' % (sem_vox.shape[0], n_vox))
+    n_seg = int(pred_bbs.shape[0])
+    # torch.mode per segment (detection_net.py:399-409): the lowest class on ties
+    hist = torch.empty(max(n_seg * NUM_CLASSES, 1), dtype=torch.int32, device=dev)
+    mode = torch.zeros(max(n_seg, 1), dtype=torch.int32, device=dev)
+    _call('b2m_seg_mode', s2v.int().contiguous().data_ptr(), sem_vox.data_ptr(), n_vox, n_seg, NUM_CLASSES, hist.data_ptr(), mode.data_ptr())
+    fg_dev = net.is_foreground(mode[:n_seg])
+    boxes = pred_bbs.detach().to(dev, torch.float32)[fg_dev].contiguous()
+    if boxes.shape[0] == 0:
+        raise ValueError('NMS_clustering needs at least one box (the reference raises on n == 0 as well)')
+    fg_slot = torch.where(fg_dev, torch.cumsum(fg_dev.int(), 0) - 1, torch.full_like(fg_dev.int(), -1)).int()
+    v2p = torch.as_tensor(np.asarray(batch['vox2point'][0])).long().to(dev).contiguous()
+    return dict(name=batch['scene'][0]['name'], idx=0, s2v=s2v, n_vox=n_vox, fg_slot=fg_slot, boxes=boxes, n_fg=int(boxes.shape[0]),
+                words=(n_vox + 63) // 64, v2p=v2p, n_pts=int(v2p.shape[0]), sem_pts=sem_vox[v2p].contiguous())
+
+
+def s3dis_stage(d, r, k_rows, mask_bin_th, clock=contextlib.nullcontext):
+    """One (cluster_th, mask_bin_th) stage of one room: the first k_rows clusters of ``r`` projected on the voxels, gathered to
+    the points, their classes (13-class vote on the points) and ONE greedy merge.  Returns (owner int32 (n_pts): the row that took
+    the point or -1, prop_sem int32 (k_rows), accepted int32 (k_rows), masks uint8 (k_rows, n_pts)), all on the device.
+    clock(name): a context manager around the 'projection' (project, gather, pack, vote) and the 'paint' part."""
+    from . import eval_s3dis as S
+    dev = d['boxes'].device
+    n = d['n_pts']
+    pwords = (n + 63) // 64
+    with clock('projection'):
+        sel = torch.arange(max(k_rows, 1), dtype=torch.int32, device=dev)
+        bits = torch.empty((max(k_rows, 1), max(d['words'], 1)), dtype=torch.int64, device=dev)
+        masks = torch.empty((k_rows, n), dtype=torch.uint8, device=dev)
+        pbits = torch.empty((max(k_rows, 1), max(pwords, 1)), dtype=torch.int64, device=dev)
+        prop_sem = torch.zeros(max(k_rows, 1), dtype=torch.int32, device=dev)
+        if k_rows:
+            _call('b2m_mask_project', r.heat.data_ptr(), d['n_fg'], sel.data_ptr(), k_rows, d['fg_slot'].data_ptr(), d['s2v'].data_ptr(),
+                  d['n_vox'], float(mask_bin_th), bits.data_ptr(), d['words'])
+            _call('b2m_mask_gather', bits.data_ptr(), d['words'], None, k_rows, d['v2p'].data_ptr(), n, masks.data_ptr())
+            _call('b2m_mask_pack', masks.data_ptr(), k_rows, n, pbits.data_ptr(), pwords)
+            _call('b2m_label_hist', pbits.data_ptr(), pwords, None, k_rows, d['sem_pts'].data_ptr(), n, S.NUM_CLASSES, prop_sem.data_ptr())
+    with clock('paint'):
+        inst = torch.empty(n, dtype=torch.int32, device=dev)
+        accepted = torch.zeros(max(k_rows, 1), dtype=torch.int32, device=dev)
+        unlabeled = torch.empty(max(pwords, 1), dtype=torch.int64, device=dev)
+        _call('b2m_paint_proposals', pbits.data_ptr(), pwords, k_rows, prop_sem.data_ptr(), n, S.SEM_MIN, S.KEEP_RATIO, S.MIN_POINTS,
+              unlabeled.data_ptr(), inst.data_ptr(), None, accepted.data_ptr())
+        owner = torch.where(inst > 0, inst - 1, torch.full_like(inst, -1)).contiguous()
+    return owner, prop_sem[:k_rows], accepted[:k_rows], masks
+
+
+def s3dis_prefix_tail(owner, prop_sem, bg, sem, ks, n_inst, gi, gt_class, gt_size, tp, fp, index=None, min_points=None, label_setting=-1):
+    """b2m_s3dis_prefix_tail: the true / false positives of every prefix length of ``ks`` are ADDED to tp / fp (int32 (S, 13), device).
+    gt_size (G) int32: the evaluation points of every ground-truth instance (``_s3dis_ground_truth`` counts them once per room).
+    label_setting >= 0: also returns that setting's (instances, semantics) at the evaluation points."""
+    from . import eval_s3dis as S
+    dev = owner.device
+    ks = np.ascontiguousarray(ks, np.int32)
+    n, n_eval = int(owner.shape[0]), int(gi.shape[0])
+    k_rows, n_gt = int(prop_sem.shape[0]), int(gt_class.shape[0])
+    size = _lib.load().b2m_s3dis_prefix_tail_workspace(k_rows, len(ks), int(n_inst), n_gt) if 1 <= len(ks) <= 64 else 0
+    if size < 0:
+        raise _lib.B2MError('b2m_s3dis_prefix_tail: %d settings x %d instances x %d ground-truth instances exceed the tables (%d entries)'
+                            % (len(ks), n_inst, n_gt, S.JOINT_HIST_MAX))
+    work = torch.empty(max(size // 4, 1), dtype=torch.int32, device=dev)
+    inst_out = sem_out = None
+    if label_setting >= 0:
+        inst_out = torch.full((n_eval,), -1, dtype=torch.int32, device=dev)
+        sem_out = torch.full((n_eval,), -1, dtype=torch.int32, device=dev)
+    _call('b2m_s3dis_prefix_tail', owner.data_ptr(), prop_sem.data_ptr() if k_rows else None, k_rows, bg.data_ptr(), sem.data_ptr(), n,
+          ks.ctypes.data, len(ks), int(n_inst), int(S.MIN_POINTS if min_points is None else min_points), gi.data_ptr(),
+          gt_class.data_ptr() if n_gt else None, gt_size.data_ptr() if n_gt else None, n_gt,
+          None if index is None else index.data_ptr(), n_eval, work.data_ptr(),
+          tp.data_ptr(), fp.data_ptr(), int(label_setting), None if inst_out is None else inst_out.data_ptr(),
+          None if sem_out is None else sem_out.data_ptr())
+    return (inst_out, sem_out) if label_setting >= 0 else None
+
+
+def _s3dis_ground_truth(labels, dev):
+    """Dense index of the ground-truth instance of every evaluation point (ascending ids), the class of every instance (most
+    frequent, lowest on ties: scipy.stats.mode, s3dis_util.py:233-238), its points and the instances per class -- once per room, on the
+    device."""
+    from . import eval_s3dis as S
+    g_ins, g_sem = S._i32(labels['instances'], dev).reshape(-1), S._i32(labels['semantics'], dev).reshape(-1)
+    vals, gi = S._dense(g_ins)
+    G = int(vals.numel())
+    if G == 0:
+        none = torch.zeros(0, dtype=torch.int32, device=dev)
+        return gi, none, none, torch.zeros(S.NUM_CLASSES, dtype=torch.int64, device=dev)
+    hist = S.joint_hist(gi, g_sem, G, S.NUM_CLASSES).long()
+    key = hist * 16 + (15 - torch.arange(S.NUM_CLASSES, device=dev))       # distinct per row: the largest count, then the lowest class
+    gt_class = key.argmax(1).int().contiguous()
+    gt_size = S.joint_hist(gi, None, G)[:, 0].contiguous()
+    return gi, gt_class, gt_size, torch.bincount(gt_class.long(), minlength=S.NUM_CLASSES)[:S.NUM_CLASSES]
+
+
+class _StageClock:
+    """clock(name): a context manager that adds the device milliseconds of its body to ``timing[name]`` (HIP events; it waits for
+    the second one, so a timed search is a pass of its own)."""
+
+    def __init__(self, timing):
+        self.timing = timing
+
+    def __call__(self, name):
+        return _StageSpan(self.timing, name)
+
+
+class _StageSpan:
+    def __init__(self, timing, name):
+        self.timing, self.name = timing, name
+
+    def __enter__(self):
+        self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self.a.record()
+
+    def __exit__(self, *exc):
+        self.b.record()
+        self.b.synchronize()
+        self.timing[self.name] = self.timing.get(self.name, 0.0) + self.a.elapsed_time(self.b)
+
+
+def s3dis_param_search(model, batches, grid, full_rooms=None, per_class=False, timing=None):
+    """Score every setting of ``grid`` with the S3DIS instance metric (mPrec / mRec, ``eval_s3dis.evaluate_rooms``) over all
+    ``batches`` of ONE room each (batch dicts, predicted here, or ``(batch, pred)`` pairs).
+
+    Per room: one forward, one ``clustering_for_background`` (the wall DBSCAN depends on no threshold), the ground-truth tables;
+    per cluster_th one clustering; per (cluster_th, mask_bin_th) one projection + point gather + class vote + ``b2m_paint_proposals``
+    over the rows of the smallest score_th (``s3dis_stage``), then ``b2m_s3dis_prefix_tail`` for all score settings.  tp / fp /
+    total_gt accumulate over the rooms on the device and come to the host in ONE read at the end.  Sizes still cross per room and
+    per cluster_th, as on the one-setting route: the number of wall clusters and the largest background id (they size the tables),
+    and the clusters' scores, from which the prefix lengths are taken on the host.
+
+    ``grid.mask_nms_th`` is accepted and IGNORED: this flow has no mask NMS (detection_net.py:449-451), every value gives the same
+    result.  With ``cfg.full_resolution`` the unsampled rooms come through ``full_rooms`` as for ``evaluate_rooms``.
+
+    Returns an ``S3DISSweepResult``: mprec, mrec (n_cluster, n_score, n_bin) float64 -- the same float64 divisions and np.mean as
+    the reference, 0 / 0 is NaN; grid; with per_class also precision, recall (..., 13) and the integer tables tp, fp (..., 13),
+    total_gt (13).  ``.best()`` picks a setting.  timing (for tools/bench_param_sweep.py): a dict that receives the device milliseconds
+    per stage; such a search waits after every stage."""
+    from . import eval_s3dis as S
+    cfg = model.cfg
+    net = model.detection_model
+    full = bool(getattr(cfg, 'full_resolution', False))
+    if full and full_rooms is None:
+        raise NotImplementedError('s3dis_param_search: cfg.full_resolution needs the unsampled rooms: pass full_rooms= (a sequence '
+                                  'aligned with the batches of (scene_full, labels_full), or a callable name -> (scene_full, labels_full))')
+    _lib.require_gpu()
+    dev = torch.device('cuda', torch.cuda.current_device())
+    nc, ns, nb, _ = grid.shape
+    tp = torch.zeros((nc, nb, ns, S.NUM_CLASSES), dtype=torch.int32, device=dev)
+    fp = torch.zeros_like(tp)
+    total_gt = torch.zeros(S.NUM_CLASSES, dtype=torch.int64, device=dev)
+
+    clock = _StageClock(timing) if timing is not None else contextlib.nullcontext
+    for i, item in enumerate(batches):
+        with clock('forward'):
+            batch, pred = item if isinstance(item, (tuple, list)) else \
+                (item, model.get_prediction(item, with_grad=False, to_cpu=True, min_size=True))
+        d = _s3dis_room(net, batch, pred, cfg, dev)
+        scene, labels = batch['scene'][0], batch['labels'][0]
+        with clock('dbscan'):
+            bg = S.clustering_for_background(d['sem_pts'], scene['positions'], scene['normals']).contiguous()
+        index = None
+        if full:
+            scene_full, labels = full_rooms(scene['name']) if callable(full_rooms) else full_rooms[i]
+            index = S.sparse2dense(scene_full['positions'], scene['positions']).contiguous()
+        gi, gt_class, gt_size, per_class_gt = _s3dis_ground_truth(labels, dev)
+        if gi.shape[0] != (d['n_pts'] if index is None else index.shape[0]):
+            raise ValueError('%s: %d ground-truth labels for %d evaluation points' % (d['name'], gi.shape[0],
+                                                                                    d['n_pts'] if index is None else index.shape[0]))
+        total_gt += per_class_gt
+        bg_top = int(bg.max().item()) if d['n_pts'] else 0
+        for ci, cth in enumerate(grid.cluster_th):
+            with clock('clustering'):
+                rs, cl = _cluster([d], cth, grid.score_th)
+            ks = cl[0]['ks']
+            k_rows = int(ks[0])
+            for bi, bth in enumerate(grid.mask_bin_th):
+                owner, prop_sem, _, _ = s3dis_stage(d, rs[0], k_rows, bth, clock=clock)
+                with clock('tail'):
+                    s3dis_prefix_tail(owner, prop_sem, bg, d['sem_pts'], ks, k_rows + max(bg_top, 0) + 1, gi, gt_class, gt_size, tp[ci, bi],
+                                      fp[ci, bi], index=index)
+    host = torch.cat([tp.reshape(-1).long(), fp.reshape(-1).long(), total_gt]).cpu().numpy()          # the one host read
+    m = nc * nb * ns * S.NUM_CLASSES
+    tp_h = host[:m].reshape(nc, nb, ns, S.NUM_CLASSES).transpose(0, 2, 1, 3).copy()
+    fp_h = host[m:2 * m].reshape(nc, nb, ns, S.NUM_CLASSES).transpose(0, 2, 1, 3).copy()
+    gt_h = host[2 * m:]
+    precision, recall = np.zeros(tp_h.shape), np.zeros(tp_h.shape)
+    mprec, mrec = np.zeros(tp_h.shape[:3]), np.zeros(tp_h.shape[:3])
+    with np.errstate(all='ignore'):
+        for st in itertools.product(range(nc), range(ns), range(nb)):      # s3dis_util.py:308-320, :338, setting by setting
+            t, f = tp_h[st].astype(np.float64), fp_h[st].astype(np.float64)
+            recall[st] = t / gt_h.astype(np.float64)
+            precision[st] = t / (t + f)
+            mprec[st], mrec[st] = np.mean(precision[st]), np.mean(recall[st])
+    out = S3DISSweepResult(mprec=mprec, mrec=mrec, grid=grid)
+    if per_class:
+        out.update(precision=precision, recall=recall, tp=tp_h, fp=fp_h, total_gt=gt_h)
     return out

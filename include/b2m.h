@@ -764,6 +764,40 @@ int b2m_paint_proposals(const uint64_t* bits, int64_t words, int32_t k, const in
 #define B2M_JOINT_HIST_MAX (1 << 24)
 int b2m_joint_hist(const int32_t* a, const int32_t* b, int64_t n, int32_t na, int32_t nb, int32_t* hist, void* stream);
 
+/* The S3DIS metric of EVERY score prefix of one (cluster_th, mask_bin_th) stage of one room (box2mask_amd/param_search.py,
+ * s3dis_param_search; the rule and its edges: profiles/s3dis_sweep_rule.md, tests/_s3dis_sweep_rule.py).  The merge of
+ * evaluation.py:178-193 is prefix-closed -- whether proposal i is accepted depends on the proposals before i only -- so ONE
+ * b2m_paint_proposals over the k_rows proposals of the smallest score_th gives, per sampled point, its owner, and setting s
+ * (the first k[s] proposals) is that painting restricted to the owners below k[s].  Per setting s < n_set, in this order:
+ *   1. point p is painted when 0 <= owner[p] < k[s]: instance owner[p] + 1, class prop_sem[owner[p]]; else instance -1 and the
+ *      predicted class sem[p] (evaluation.py:192-193);
+ *   2. max_id = the largest painted instance of the setting, -1 without one (evaluation.py:197);
+ *   3. a point with bg[p] > 0 and bg[p] + max_id > 0 gets instance bg[p] + max_id; its class stays (evaluation.py:198-199: with
+ *      max_id = -1 the ceiling's id 1 drops to 0 and is not written);
+ *   4. over the n SAMPLED points, every (instance >= 0, class in 0 .. 12) pair with fewer than min_points points loses them:
+ *      instance -1 (evaluation.py:200-210);
+ *   5. over the n_eval EVALUATION points q -- sampled point index[q], or q itself with index == NULL (evaluation.py:213-222) --
+ *      per instance >= 0 its size, its class = the most frequent class of its points (lowest on ties) and its common points with
+ *      every ground-truth instance gi[q] in [0, n_gt); the instance adds 1 to tp[s * 13 + class] when a ground-truth instance g
+ *      with gt_class[g] == class has 3 * inter >= size + gt_size[g] (inter / union >= 0.5, s3dis_util.py:280-296), else to fp.
+ *      gt_size[g] = the number of evaluation points with gi == g: it depends on no setting, the caller counts it once per room.
+ * tp / fp: int32[n_set][13], ADDED to (the caller zeroes them before the first room).  owner: int32[n], -1 or a row of the
+ * painting (b2m_paint_proposals' inst - 1); an owner at or above k_rows counts as -1.  bg: as clustering_for_background leaves it.
+ * k_host: n_set prefix lengths in HOST memory, not increasing, k_host[0] <= k_rows, 1 <= n_set <= B2M_SWEEP_MAX_TH.  n_inst: every
+ * instance id lies below it (k_rows + the largest bg + 1 is enough; an id at or above it counts as -1).  index: int64[n_eval],
+ * repeats and unnamed sampled points allowed; a value outside [0, n) gives instance -1 and class -1.  gi outside [0, n_gt) joins no
+ * ground-truth instance.  label_setting >= 0: that setting's labels at the evaluation points go to inst_out / sem_out
+ * (int32[n_eval], either may be NULL); -1: none.  workspace: b2m_s3dis_prefix_tail_workspace(...) bytes (-1: out of range), zeroed
+ * here.  Refused: n_set outside 1 .. 64, increasing k, k[0] > k_rows, n_set * n_inst * max(13, n_gt) > B2M_JOINT_HIST_MAX.
+ * n == 0 or n_eval == 0: nothing is launched or written.  Integer adds and stores of one value only: nothing depends on the order
+ * of the atomics, two runs give the same tables. */
+int64_t b2m_s3dis_prefix_tail_workspace(int32_t k_rows, int32_t n_set, int32_t n_inst, int32_t n_gt);
+int b2m_s3dis_prefix_tail(const int32_t* owner, const int32_t* prop_sem, int32_t k_rows, const int32_t* bg, const int32_t* sem,
+                          int64_t n, const int32_t* k_host, int32_t n_set, int32_t n_inst, int32_t min_points, const int32_t* gi,
+                          const int32_t* gt_class, const int32_t* gt_size, int32_t n_gt, const int64_t* index, int64_t n_eval,
+                          void* workspace, int32_t* tp, int32_t* fp, int32_t label_setting, int32_t* inst_out, int32_t* sem_out,
+                          void* stream);
+
 /* ---------------------------------------------------------------- ScanNet AP: matching and curves (box2mask_amd/eval_match.py)
  * The second half of utils/eval_metric.py -- what assign_instances_for_scan (:281-345) derives from the intersection counts, the
  * greedy matching of evaluate_matches (:102-199) for the ten overlaps and eighteen classes, the precision / recall curve and the

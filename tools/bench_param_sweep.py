@@ -2,7 +2,7 @@
 path: scenes of ~150 k voxels from synth.make_batch, votes as bench.py's votes leg makes them (every segment votes for its object's
 box with 2.5 cm noise, score logits ~ N(0, 2)), the default 6 x 5 x 4 x 5 grid.
 
-    python tools/bench_param_sweep.py [--scenes 8] [--voxels 150000] [--loop-settings 12] [--metric scannet|arkit]
+    python tools/bench_param_sweep.py [--scenes 8] [--voxels 150000] [--loop-settings 12] [--metric scannet|arkit|s3dis]
 
 Reports the device ms of the sweep's stages (HIP events round every launch, a pass of its own: the events serialise the stream),
 the wall time of the sweep up to the tables, the wall time of the host matching of all settings, and the looped path --
@@ -16,6 +16,13 @@ timed searches after a warm-up) and the largest difference between the two route
 rooms' furniture boxes as ground truth): device ms per stage with the hull passes (b2m_mask_hulls_index_batch) and the IoU calls,
 the wall time of the tables and of the whole search, and the looped path -- Model.pred2mask + eval_detection.arkitscenes_eval per
 setting -- on `--loop-settings` settings, scaled to the grid, with its mAPs compared with the sweep's.
+
+--metric s3dis: `--scenes` synthetic S3DIS-shaped rooms (batches of one; the rooms of tools/bench_eval_s3dis.py: floor -> class 1, three
+walls -> wall, one -> ceiling, furniture -> classes 3 .. 12, per-voxel semantics with 2 % wrong voxels), the 6 x 5 x 4 grid of config.py
+(mask_nms_th has no effect in this flow) through param_search.s3dis_param_search, beside the same settings one by one through
+eval_s3dis.evaluate_rooms with cfg.eval_ths set (`--loop-settings`, 0 = all 120) in the same process.  Both routes read the same
+synthetic head outputs: the network forward is in neither time.  Device ms per stage (DBSCAN, clustering, projection / gather,
+paint, tail) from a pass of its own with HIP events round every stage; mPrec / mRec of the looped settings are compared bit for bit.
 """
 import argparse
 import json
@@ -55,8 +62,10 @@ def main(argv=None):
     ap.add_argument('--voxels', type=int, default=150000)
     ap.add_argument('--loop-settings', type=int, default=12, help='settings the looped path is timed on, scaled to the grid (0 = all)')
     ap.add_argument('--device-runs', type=int, default=5, help='timed searches with matching=device (median)')
-    ap.add_argument('--metric', choices=('scannet', 'arkit'), default='scannet')
+    ap.add_argument('--metric', choices=('scannet', 'arkit', 's3dis'), default='scannet')
     args = ap.parse_args(argv)
+    if args.metric == 's3dis':
+        return s3dis_leg(args)
     cfg = scannet_config()
     model = Model(cfg, *synth.scannet_tables())
     model.eval()
@@ -241,6 +250,101 @@ def arkit_leg(args, cfg, model):
            'looped_settings_timed': len(chosen), 'looped_pred2mask_s': round(t_mask, 3), 'looped_arkitscenes_eval_s': round(t_eval, 3),
            'looped_scaled_to_grid_s': round((t_mask + t_eval) * scale, 1), 'looped_is_scaled': len(chosen) != n_set,
            'looped_map_equals_sweep_map': agree}
+    print(json.dumps(out))
+
+
+def s3dis_room(seed, voxels, cfg):
+    """One S3DIS-shaped room as a batch of one and its head outputs: the votes of bench.py's votes leg, per-voxel semantics."""
+    batch = synth.make_batch(1, seed0=seed, target_voxels=voxels)
+    pred, _ = synthetic_votes(batch, cfg, seed=7 + seed)
+    pred.pop(cfg.mlp_semantics, None)
+    raw = synth.make_scene(seed, target_voxels=voxels, points_only=True)
+    v2p = np.asarray(batch['vox2point'][0])
+    assert len(raw['positions']) == len(v2p)
+    inst = raw['labels']['seg2inst'][raw['segments']].astype(np.int64)
+    cls = raw['labels']['per_instance_semantics'][inst]
+    sem = np.where(cls == 2, 1, 3 + inst % 10)                          # floor -> 1, furniture -> 3 .. 12
+    wall = cls == 1
+    sem[wall] = np.where(raw['normals'][wall, 0] < 0, 0, 2)              # three walls predicted as wall, one as ceiling
+    n_vox = int(batch['vox_coords'].shape[0])
+    vox_sem = np.zeros(n_vox, np.int64)
+    vox_sem[v2p] = sem
+    rng = np.random.default_rng(seed)
+    wrong = rng.random(n_vox) < 0.02
+    vox_sem[wrong] = rng.integers(0, 13, int(wrong.sum()))
+    pred[cfg.mlp_per_vox_semantics] = torch.from_numpy(np.eye(13, dtype=np.float32)[vox_sem])
+    batch['scene'][0]['positions'], batch['scene'][0]['normals'] = raw['positions'], raw['normals']
+    batch['labels'] = [{'semantics': sem, 'instances': inst}]
+    for k in ('input_location', 'batch_ids'):
+        batch[k] = batch[k].cpu()
+    return batch, pred
+
+
+class _Votes:
+    """evaluate_rooms' model: the synthetic head outputs instead of a forward, the real votes -> masks pass."""
+
+    def __init__(self, model, preds):
+        self.model, self.cfg, self.preds = model, model.cfg, preds
+
+    def get_prediction(self, batch, **kw):
+        return {k: v.clone() for k, v in self.preds[batch['scene'][0]['name']].items()}
+
+    def pred2mask(self, batch, pred, mode):
+        return self.model.pred2mask(batch, pred, mode)
+
+
+def s3dis_leg(args):
+    from box2mask_amd import eval_s3dis
+    cfg = scannet_config(network_heads=['mlp_offsets', 'mlp_bounds', 'mlp_bb_scores', 'mlp_per_vox_semantics'])
+    ids = torch.arange(13).long()
+    model = Model(cfg, torch.Tensor(np.arange(13)), ids, ids.clone(), (lambda s_: s_ > 2))
+    model.eval()
+    note = lambda msg: print('[bench_param_sweep] ' + msg, file=sys.stderr, flush=True)
+    items = [s3dis_room(s_, args.voxels, cfg) for s_ in range(args.scenes)]
+    for i, (b, _) in enumerate(items):
+        b['scene'][0]['name'] = 'room%d' % i
+    grid = param_search.ThresholdGrid.from_cfg(cfg)
+    nc, ns, nb, _ = grid.shape
+    n_set = nc * ns * nb
+    note('s3dis: %d rooms, %s points, %d settings' % (args.scenes, [len(b['vox2point'][0]) for b, _ in items], n_set))
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)
+        param_search.s3dis_param_search(model, items, grid)                             # warm-up
+        res, sweep_s = wall(lambda: param_search.s3dis_param_search(model, items, grid, per_class=True))
+        stages = {}
+        param_search.s3dis_param_search(model, items, grid, timing=stages)             # a pass of its own: the events synchronise
+    note('sweep %.3f s; the looped path ...' % sweep_s)
+    settings = [(ci, si, bi) for ci in range(nc) for si in range(ns) for bi in range(nb)]
+    n_loop = n_set if args.loop_settings <= 0 else min(args.loop_settings, n_set)
+    chosen = [settings[i] for i in np.unique(np.linspace(0, n_set - 1, n_loop).round().astype(int))]
+    votes = _Votes(model, {b['scene'][0]['name']: p for b, p in items})
+    batches = [b for b, _ in items]
+    saved, agree, t_loop = cfg.eval_ths, True, 0.0
+    cfg.eval_ths = grid.eval_ths(*chosen[0], 0)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)
+        eval_s3dis.evaluate_rooms(votes, batches)                                       # warm-up
+        for st in chosen:
+            cfg.eval_ths = grid.eval_ths(*st, 0)
+            (mprec, mrec, _, _), dt = wall(lambda: eval_s3dis.evaluate_rooms(votes, batches))
+            t_loop += dt
+            if (chosen.index(st) + 1) % 10 == 0:
+                note('%d of %d settings one by one: %.1f s' % (chosen.index(st) + 1, len(chosen), t_loop))
+            agree &= bool(np.array_equal(res['mprec'][st], mprec, equal_nan=True) and np.array_equal(res['mrec'][st], mrec, equal_nan=True))
+    cfg.eval_ths = saved
+    scale = n_set / len(chosen)
+    looped = t_loop * scale
+    order = ('dbscan', 'clustering', 'projection', 'paint', 'tail')
+    out = {'metric': 's3dis', 'rooms': args.scenes, 'points': [int(len(b['vox2point'][0])) for b, _ in items],
+           'voxels': [int(b['vox_coords'].shape[0]) for b, _ in items], 'grid': [nc, ns, nb], 'settings': n_set,
+           'stages_device_ms': {k: round(float(stages.get(k, 0.0)), 3) for k in order},
+           'stage_calls': {'dbscan': args.scenes, 'clustering': args.scenes * nc, 'projection': args.scenes * nc * nb,
+                           'paint': args.scenes * nc * nb, 'tail': args.scenes * nc * nb},
+           'sweep_wall_s': round(sweep_s, 4), 'looped_settings_timed': len(chosen), 'looped_wall_s': round(t_loop, 3),
+           'looped_scaled_to_grid_s': round(looped, 2), 'looped_is_scaled': len(chosen) != n_set,
+           'speedup': round(looped / sweep_s, 2), 'stage_ratio': round(n_set / (nc * nb), 2),
+           'looped_metric_equals_sweep': agree, 'best': res.best(),
+           'finite_settings': int(np.isfinite(res['mprec']).sum())}
     print(json.dumps(out))
 
 
