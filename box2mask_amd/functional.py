@@ -496,7 +496,10 @@ def wgrad_up_over_down_map() -> bool:
 # leaves slots empty, and a conv_fwd_flow wave needs 12 KiB of LDS where a weight-gradient wave needs none), so the two
 # fill each other's gaps.  B2M_WGRAD_STREAM=0 keeps everything on one stream; the deterministic mode always does (its
 # partial-sum workspace is shared by all layers in stream order).
-_side = {'streams': {}, 'armed': False}
+#   seen:         id() of the weights whose gradient was issued since the current backward pass began (cleared at its end)
+#   early_joins:  how often the main stream had to wait for the side stream INSIDE a backward pass (issue_wgrad); the plain step
+#                 loop never does -- tests/test_gpu_grad_protocol.py reads the counter
+_side = {'streams': {}, 'armed': False, 'seen': set(), 'early_joins': 0}
 
 
 def wgrad_on_side_stream() -> bool:
@@ -519,9 +522,34 @@ def join_side_streams():
         torch.cuda.current_stream(dev).wait_stream(st)
 
 
-def issue_wgrad(run, dy, x1, x2, dw):
-    """Runs `run()`, the weight-gradient launches of one layer (they read dy, x1 and x2 -- x2 may be None -- and add into dw):
-    on the side stream where wgrad_on_side_stream() says so, else inline.  The one place that keeps the side stream's rules."""
+def _end_of_backward():
+    # (a backward pass that dies half-way never gets here: the ids it leaves behind cost the next pass a wait each, no more)
+    _side['seen'].clear()
+    join_side_streams()
+
+
+def issue_wgrad(run, dy, x1, x2, dw, weight=None):
+    """Runs `run()`, the weight-gradient launches of one layer (they read dy, x1 and x2 -- x2 may be None -- and add into dw, the
+    gradient of `weight`): on the side stream where wgrad_on_side_stream() says so, else inline.  The one place that keeps the
+    side stream's rules:
+
+      1. the side stream starts behind everything the main stream has queued (dy, x, the zeroed slot);
+      2. the main stream joins the side stream at the END of the backward pass (an engine callback), so whatever reads a
+         gradient after backward() / autograd.grad() returns reads it complete;
+      3. where autograd itself reads `dw` BEFORE that end, the main stream waits right behind the launch.  That is the case
+         exactly when autograd has something to add `dw` to: `weight.grad` exists already (gradients kept across passes,
+         zero_grad(set_to_none=False): AccumulateGrad runs `weight.grad += dw` on the main stream as soon as this node returns),
+         or this is a later gradient of the same weight within one backward pass (a weight shared by two layers, two forward
+         passes summed into one loss, a retained graph run twice: the engine's input buffer adds the two tensors).  Otherwise
+         -- the plain step loop: `.grad is None`, first use -- autograd only adopts the tensor, reads nothing, and no wait is
+         placed: the schedule of that loop is what it was.  The wait covers every earlier launch on the side stream too, so the
+         first gradient of a shared weight is complete when the second one is added to it.
+         (That the kernels on two streams really overlap an add of autograd's at a given size is a matter of timing: a test that
+         passes does not prove this rule, the argument above does; tests/test_gpu_grad_protocol.py guards it and checks through
+         `_side['early_joins']` which branch ran.)
+
+    A caller without `weight` (None) is treated as case 3.  Gradient hooks that read `.grad` or `dw` during backward are outside
+    these rules: such a hook must call join_side_streams() first, as parallel.GradAllReduce._launch does."""
     if not wgrad_on_side_stream():
         run()
         return
@@ -532,9 +560,14 @@ def issue_wgrad(run, dy, x1, x2, dw):
     for t in (dy, x1, x2, dw):                  # the allocator must not hand these out again before the side stream is done
         if t is not None:
             t.record_stream(side)
+    if weight is None or weight.grad is not None or id(weight) in _side['seen']:
+        main.wait_stream(side)                  # rule 3: autograd adds dw on the main stream before the end-of-backward join
+        _side['early_joins'] += 1
+    if weight is not None:
+        _side['seen'].add(id(weight))
     if not _side['armed']:                      # once per backward pass: the main stream joins at its end
         _side['armed'] = True
-        torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
+        torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
 
 
 class _SparseConv(torch.autograd.Function):
@@ -611,7 +644,7 @@ class _SparseConv(torch.autograd.Function):
                 wgrad_raw(x1, dy, ctx.rb_f, K, dw3, 0, c1)
                 if x2 is not None:
                     wgrad_raw(x2, dy, ctx.rb_f, K, dw3, c1, x2.shape[1])
-            issue_wgrad(run, dy, x1, x2, dw)
+            issue_wgrad(run, dy, x1, x2, dw, weight)
         if bias is not None and ctx.needs_input_grad[3]:
             db = grad_slot(bias)
             if db is not None and db.shape == (1, cout):

@@ -7,12 +7,21 @@ launches).  With the arena a step zeroes the whole buffer with ONE memset, the b
 their slots, autograd adopts the slot views as `.grad`, and the all-reduce runs in place on contiguous bucket
 ranges of the same memory (box2mask_amd/parallel.py).
 
-Aliasing rule: a buffer may only be cleared while no live `.grad` points into it.  `optimizer.zero_grad()`
-(set_to_none=True, the torch default the reference's train_step relies on, /root/reference/models/training.py:63-70)
-drops the views, so in the normal loop buffer 0 is reused every step.  If gradients are kept across backward
-passes (accumulation), `.grad` still owns one buffer and the next pass takes the other one; autograd then adds the
-new views into the old ones in place.  A caller that keeps a reference to an old `.grad` tensor beyond the second
-following backward pass sees it overwritten -- the one behavioural difference to separately allocated gradients.
+Aliasing rule: a buffer is cleared only while nothing handed out from it can still be read -- no live `.grad` points
+into it AND no view `slot()` handed out of it is still alive.  The two halves are the two ways a gradient leaves a backward
+pass.  `backward()`: AccumulateGrad keeps a detached alias of the slot view as `.grad` and the view object itself dies with
+the pass, so the pointer check finds it.  `torch.autograd.grad()`: the tensors it returns ARE the slot views, `.grad` stays
+None, and only the (weak) references the arena keeps to the views it handed out tell that somebody still holds them.
+`optimizer.zero_grad()` (set_to_none=True, the torch default the reference's train_step relies on,
+/root/reference/models/training.py:63-70) drops the views, so in the normal loop buffer 0 is reused every step.  If
+gradients are kept across backward passes (accumulation, zero_grad(set_to_none=False), results of autograd.grad still
+held), they own one buffer and the next pass takes the other one; autograd then adds the new views into the old `.grad`
+in place, which stays the memory it was after the first pass.  When both buffers are owned the arena gives up for the
+pass and the operators allocate.  Within a pass a slot is handed out once (`slot`): a second backward operator of the same
+parameter -- a shared weight, two forward passes summed into one loss, a second backward() over a retained graph --
+allocates, and autograd adds.  What a caller holds is therefore never cleared or overwritten behind its back; a kept
+`.grad` tensor changes only the way torch's own does, by the in-place adds of later backward passes
+(tests/test_grad_protocol_rule.py, tests/test_gpu_grad_protocol.py pin this under nine backward protocols).
 """
 from __future__ import annotations
 
@@ -42,15 +51,20 @@ class GradArena:
         self.buffers = [None, None]      # allocated on first use (the second one only if gradients are ever kept)
         self.current = None              # index of the buffer of the pass in flight
         self.handed = set()              # id(p) of the slots handed out since the last begin_pass
+        self.views = [[], []]            # per buffer: weak references to the views handed out of it (see _owned)
         for p in self.params:
             _registry[id(p)] = (weakref.ref(p), weakref.ref(self), id(p))
 
     # ---- per pass
     def _owned(self, j):
-        """True if some live .grad points into buffer j."""
+        """True if some live .grad points into buffer j, or a view handed out of it is still alive (the results of
+        torch.autograd.grad are the handed views themselves: no .grad points at them)."""
         buf = self.buffers[j]
         if buf is None:
             return False
+        self.views[j] = [r for r in self.views[j] if r() is not None]
+        if self.views[j]:
+            return True
         base = buf.data_ptr()
         for p in self.params:
             g = p.grad
@@ -59,18 +73,19 @@ class GradArena:
         return False
 
     def begin_pass(self):
-        """Pick a buffer no live gradient points into and clear it (one memset).  Called once per forward pass,
+        """Pick a buffer nothing handed out earlier still views (_owned) and clear it (one memset).  Called once per forward pass,
         before any backward operator of that pass can run."""
         self.handed.clear()
         j = 0 if not self._owned(0) else 1
         if j == 1 and self._owned(1):
-            # gradients from two earlier passes are both alive (the caller re-assigned .grad by hand): give up the
-            # arena for this pass, the operators fall back to separately allocated gradients
+            # gradients from two earlier passes are both alive (results of autograd.grad held beside kept .grads, or .grad
+            # re-assigned by hand): give up the arena for this pass, the operators fall back to separately allocated gradients
             self.current = None
             return
         dev = self.params[0].device                      # follows Model.to(device)
         if self.buffers[j] is None or self.buffers[j].device != dev:
             self.buffers[j] = torch.empty(self.size, dtype=torch.float32, device=dev)
+            self.views[j] = []
         self.buffers[j].zero_()
         self.current = j
 
@@ -90,6 +105,7 @@ class GradArena:
         if g is not None and g.data_ptr() == view.data_ptr():
             return None          # a second backward of the same pass: .grad already lives here, it must not be its own addend
         self.handed.add(id(p))
+        self.views[self.current].append(weakref.ref(view))
         return view
 
     # ---- for the all-reduce

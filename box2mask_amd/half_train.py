@@ -281,7 +281,7 @@ class _ConvH(torch.autograd.Function):
                 _wgrad_h(x1, dy, ctx.rb_f, K, dw3, 0, inv)      # (inv: the kernel un-scales the block on its way into dW)
                 if x2 is not None:
                     _wgrad_h(x2, dy, ctx.rb_f, K, dw3, c1, inv)
-            F_.issue_wgrad(run, dy, x1, x2, dw)
+            F_.issue_wgrad(run, dy, x1, x2, dw, weight)
         return dx1, dx2, dw, None, None, None, None, None, None
 
 
