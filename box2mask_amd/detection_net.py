@@ -12,11 +12,10 @@ import torch
 from torch import nn
 
 from . import _lib
-from . import iou_nms
+from . import mask_stages
 from . import functional as F_
 from . import nn as ME
 from .resnet import BasicBlock, ResNetBase
-from .util import to_bbs_min_max
 
 _call = _lib.call
 
@@ -288,139 +287,48 @@ class SelectionNet(ResNetBase):
         the voxel->point projection are HIP kernels; only scalars and the final results cross PCIe."""
         _lib.require_gpu()
         dev = torch.device('cuda', torch.cuda.current_device())
-        pdev = pred[cfg.mlp_offsets].device
-        pred_bbs = to_bbs_min_max(batch['input_location'].to(pdev), pred[cfg.mlp_offsets], pred[cfg.mlp_bounds],
-                                  torch.nn.Sigmoid()(pred[cfg.mlp_bb_scores]))
-        if cfg.mlp_per_vox_semantics in cfg.network_heads:
-            pred_semantics = torch.argmax(pred[cfg.mlp_per_vox_semantics], 1)
-        else:
-            pred_semantics = torch.argmax(pred[cfg.mlp_semantics], 1)
-            pred_semantics = self.semantic_valid_class_ids.to(pdev)[pred_semantics].long()
-        n_class = int(max(int(self.semantic_valid_class_ids.max()) + 1, 1))
-        batch_ids = batch['batch_ids'].to(pdev)
         # The reference walks the scenes one by one (detection_net.py:390-477).  Here every stage runs for ALL scenes
         # before its (small) results are read back ONCE: clusters of the whole batch in one launch, then the score
         # filter, the mask NMS flags and the labels -- four host reads per batch instead of about ten per scene.
-        # ---------- stage 0: per-scene inputs
-        sc = []
-        vox_start = 0
-        for scene_idx, scene in enumerate(batch['scene']):
-            scene_mask = batch_ids == scene_idx
-            if cfg.do_segment_pooling:
-                seg2vox = torch.as_tensor(batch['seg2vox'][scene_idx]).long()
-            else:
-                # predictions already live on the voxels (detection_net.py:436-445 projects only `if cfg.do_segment_pooling`):
-                # the voxel of vote j IS j.  (The reference's branch then indexes per-voxel arrays with masks that have one
-                # column per FOREGROUND vote, :463 / :470, and fails on the first background voxel; here background votes are
-                # zero-padded exactly as the pooled branch does, which is the same result whenever the reference has one.)
-                seg2vox = torch.arange(int(scene_mask.sum()), dtype=torch.long)
-            n_vox = seg2vox.shape[0]
-            s2v = seg2vox.to(dev)
-            if not self.requires_voxel_outputs:
-                scene_pred_semantics = pred_semantics[scene_mask]
-                scene_pred_fg = self.is_foreground(scene_pred_semantics)
-                sem_vox = scene_pred_semantics.to(dev)[s2v]
-            else:
-                # S3DIS flow (detection_net.py:398-415): per-voxel semantics, majority vote per segment
-                sem_vox_all = pred_semantics[vox_start:vox_start + n_vox] if pred_semantics.shape[0] != n_vox \
-                    else pred_semantics
-                sem_vox = sem_vox_all.to(dev)
-                n_seg = int(s2v.max()) + 1
-                votes = torch.bincount(s2v * n_class + sem_vox, minlength=n_seg * n_class).reshape(n_seg, n_class)
-                scene_pred_fg = self.is_foreground(torch.argmax(votes, 1)).to(pdev)
-            vox_start += n_vox
-            scene_pred_bbs = pred_bbs[scene_mask][scene_pred_fg]
-            boxes = scene_pred_bbs.detach().to(dev, torch.float32).contiguous()
-            if boxes.shape[0] == 0:
-                # the reference crashes on a scene without foreground votes (torch.stack([]), iou_nms.py:103)
-                raise ValueError('NMS_clustering needs at least one box (the reference raises on n == 0 as well)')
-            fg_dev = scene_pred_fg.to(dev)
-            fg_slot = torch.where(fg_dev, torch.cumsum(fg_dev.int(), 0) - 1, torch.full_like(fg_dev.int(), -1)).int()
-            sc.append(dict(name=scene['name'], idx=scene_idx, s2v=s2v, n_vox=n_vox, sem32=sem_vox.int().contiguous(),
-                           fg=scene_pred_fg, fg_dev=fg_dev, fg_slot=fg_slot, bbs=scene_pred_bbs, boxes=boxes,
-                           n_fg=boxes.shape[0], words=(n_vox + 63) // 64))
+        # ---------- stage 0: per-scene inputs (vox2point is uploaded for the point masks of 'eval' only)
+        sc = mask_stages.scene_inputs(self, batch, pred, cfg, dev, points=mode == 'eval')
         if not sc:
             return {}
-        # ---------- stage 1: instance clusters (iou_nms.py:68-105), all scenes in one launch
-        rs = iou_nms.nmc_device_batch([d['boxes'] for d in sc], cluster_th)
-        # ---------- stage 2: score filter (detection_net.py:427-432) on the host from one read of the representatives' scores
-        rep_scores = torch.cat([d['boxes'][r.reps[:r.k].long(), 0] for d, r in zip(sc, rs)]).cpu().numpy()
-        reps_host = torch.cat([r.reps[:r.k] for r in rs]).cpu().numpy().astype(np.int64)
-        o = 0
-        for d, r in zip(sc, rs):
-            d['reps'] = reps_host[o:o + r.k]
-            scores = rep_scores[o:o + r.k]
-            o += r.k
-            sel = np.nonzero(scores > np.float32(score_th))[0] if score_filtering else np.arange(r.k)
-            d['sel'] = sel.astype(np.int64)
-        # ---------- heat-maps -> voxel masks (436-446): zero-padded background, seg2vox projection; duplicate removal
-        # (448): mask NMS, skipped for per-voxel predictions (449-451).  One launch per stage for ALL scenes: a table of
-        # B2M_MASK_DESC fields per scene (include/b2m.h) carries the scene's pointers and sizes.
         S = len(sc)
-        desc = np.zeros((S, 20), np.int64)
-        ksels = [int(d['sel'].shape[0]) for d in sc]
-        sel_all = torch.from_numpy(np.concatenate([d['sel'] for d in sc]).astype(np.int32)).to(dev) if sum(ksels) else \
-            torch.zeros(1, dtype=torch.int32, device=dev)
-        bits_all = torch.empty(max(sum(k * max(d['words'], 1) for k, d in zip(ksels, sc)), 1), dtype=torch.int64, device=dev)
-        inter_all = torch.empty(max(sum(k * k for k in ksels), 1), dtype=torch.int32, device=dev)
-        keep_all = torch.empty(max(sum(ksels), 1), dtype=torch.int32, device=dev)
+        n_class = int(max(int(self.semantic_valid_class_ids.max()) + 1, 1))
+        # ---------- stage 1: instance clusters (iou_nms.py:68-105); stage 2: score filter (detection_net.py:427-432) on the host
+        found = mask_stages.clusters(sc, cluster_th)
+        sels = [mask_stages.score_filter(conf, score_th) if score_filtering else np.arange(r.k, dtype=np.int64) for r, conf, _ in found]
+        # ---------- heat-maps -> voxel masks (436-446): zero-padded background, seg2vox projection; duplicate removal
+        # (448): mask NMS, skipped for per-voxel predictions (449-451).  One launch per stage for ALL scenes.
         do_nms = not self.requires_voxel_outputs
+        tab = mask_stages.MaskTable(sc, [r.heat for r, _, _ in found], sels, dev, keep=do_nms)
+        ksels, total_sel, max_words = tab.ksels, tab.total, max(d['words'] for d in sc)
+        desc_ptr, _ = tab.upload()
+        _call('b2m_mask_project_batch', desc_ptr, S, total_sel, max_words, float(mask_bin_th))
         keep_host = np.zeros(0, np.int32)
-        row0 = boff = ioff = 0
-        for s_, (d, r, ksel) in enumerate(zip(sc, rs, ksels)):
-            d['bits_off'] = boff
-            desc[s_, 0:9] = (r.heat.data_ptr(), d['n_fg'], sel_all.data_ptr() + 4 * row0, ksel, d['fg_slot'].data_ptr(),
-                             d['s2v'].data_ptr(), d['n_vox'], bits_all.data_ptr() + 8 * boff, d['words'])
-            desc[s_, 9] = inter_all.data_ptr() + 4 * ioff
-            desc[s_, 10] = keep_all.data_ptr() + 4 * row0 if (do_nms and ksel > 0) else 0
-            desc[s_, 18] = row0
-            row0 += ksel; boff += ksel * max(d['words'], 1); ioff += ksel * ksel
-        total_sel = row0
-        desc_dev = torch.from_numpy(desc).to(dev)
-        _call('b2m_mask_project_batch', desc_dev.data_ptr(), S, total_sel, max(d['words'] for d in sc), float(mask_bin_th))
         if do_nms and total_sel:
-            _call('b2m_mask_nms_batch', desc_dev.data_ptr(), S, max(ksels), float(mask_nms_th))
-            keep_host = keep_all[:total_sel].cpu().numpy()           # the one host read of the stage
-        o = 0
-        for d, ksel in zip(sc, ksels):
-            d['kept'] = np.nonzero(keep_host[o:o + ksel])[0].astype(np.int64) if do_nms else np.arange(ksel, dtype=np.int64)
-            o += ksel
-        # ---------- label per instance: argmax of the label histogram inside the mask (461-466)
-        kks = [int(d['kept'].shape[0]) for d in sc]
+            _call('b2m_mask_nms_batch', desc_ptr, S, max(ksels), float(mask_nms_th))
+            keep_host = tab.keep_all[:total_sel].cpu().numpy()       # the one host read of the stage
+        kept = [np.nonzero(keep_host[r0:r0 + k])[0].astype(np.int64) if do_nms else np.arange(k, dtype=np.int64)
+                for r0, k in zip(tab.row0, ksels)]
+        # ---------- label per instance: argmax of the label histogram inside the mask (461-466); masks on the points
+        kks = [int(k.shape[0]) for k in kept]
         total_kept = sum(kks)
-        kept_all = torch.from_numpy(np.concatenate([d['kept'] for d in sc]).astype(np.int32)).to(dev) if total_kept else \
+        kept_all = torch.from_numpy(np.concatenate(kept).astype(np.int32)).to(dev) if total_kept else \
             torch.zeros(1, dtype=torch.int32, device=dev)
         labels_all = torch.zeros(max(total_kept, 1), dtype=torch.int32, device=dev)
-        outs, v2ps = [], []
-        row0 = 0
-        for s_, (d, kk) in enumerate(zip(sc, kks)):
-            if mode == 'eval':
-                v2p = torch.as_tensor(batch['vox2point'][d['idx']]).long().to(dev)
-                n_pts, idx_ptr = int(v2p.shape[0]), v2p.data_ptr()
-                v2ps.append(v2p)
-            else:
-                n_pts, idx_ptr = d['n_vox'], 0
-            out = torch.empty((kk, n_pts), dtype=torch.uint8, device=dev)
-            outs.append(out)
-            desc[s_, 11:18] = (kept_all.data_ptr() + 4 * row0, kk, d['sem32'].data_ptr(), labels_all.data_ptr() + 4 * row0,
-                               idx_ptr, n_pts, out.data_ptr())
-            desc[s_, 19] = row0
-            row0 += kk
+        outs = [torch.empty((kk, d['n_pts'] if mode == 'eval' else d['n_vox']), dtype=torch.uint8, device=dev) for d, kk in zip(sc, kks)]
+        max_pts = max(int(o_.shape[1]) for o_ in outs)
+        tab.set_kept(kks, kept_all.data_ptr(), labels_all.data_ptr(), [(d.get('v2p'), int(o_.shape[1]), o_) for d, o_ in zip(sc, outs)])
         # (the scenes' voxel-major scratch images of b2m_mask_gather_batch_t ride behind the table: one upload)
-        nws = [(kk + 63) // 64 for kk in kks]
-        tb_all = torch.empty(max(sum(d['n_vox'] * nw for d, nw in zip(sc, nws)), 1), dtype=torch.int64, device=dev)
-        tb_ptrs = np.zeros(S, np.int64)
-        toff = 0
-        for s_, (d, nw) in enumerate(zip(sc, nws)):
-            tb_ptrs[s_] = tb_all.data_ptr() + 8 * toff
-            toff += d['n_vox'] * nw
-        desc_dev = torch.from_numpy(np.concatenate([desc.reshape(-1), tb_ptrs])).to(dev)
-        _call('b2m_label_hist_batch', desc_dev.data_ptr(), S, total_kept, n_class)
+        tb_all, tb_ptrs = mask_stages.voxel_major_scratch(sc, kks, dev)
+        desc_ptr, tb_ptr = tab.upload(tb_ptrs)
+        _call('b2m_label_hist_batch', desc_ptr, S, total_kept, n_class)
         if os.environ.get('B2M_MASK_GATHER_T', '1') == '1':
-            _call('b2m_mask_gather_batch_t', desc_dev.data_ptr(), S, total_kept, max(int(o_.shape[1]) for o_ in outs),
-                  max(d['words'] for d in sc), desc_dev.data_ptr() + 8 * S * 20)
+            _call('b2m_mask_gather_batch_t', desc_ptr, S, total_kept, max_pts, max_words, tb_ptr)
         else:
-            _call('b2m_mask_gather_batch', desc_dev.data_ptr(), S, total_kept, max(int(o_.shape[1]) for o_ in outs))
+            _call('b2m_mask_gather_batch', desc_ptr, S, total_kept, max_pts)
         labels_host = labels_all[:total_kept].cpu().numpy().astype('int32')
         # bytes every implementation of the four stages moves (for bench.py's roofline of the leg; nothing on the path reads it)
         self._d2m_bytes = {
@@ -432,26 +340,24 @@ class SelectionNet(ResNetBase):
         self._d2m_bytes['b2m_mask_gather_batch_t'] = self._d2m_bytes['b2m_mask_gather_batch']      # (the same operands, every one once)
         results = {}
         o = 0
-        for d, r, out in zip(sc, rs, outs):
-            kk = d['kept'].shape[0]
+        for d, (r, _, reps), sel, rows, out in zip(sc, found, sels, kept, outs):
+            kk = rows.shape[0]
             instance_labels = labels_host[o:o + kk]
             o += kk
-            final_rows = d['sel'][d['kept']]             # cluster row of every surviving instance
-            rep_rows = torch.from_numpy(d['reps'][final_rows]).to(pdev)
+            final_rows = sel[rows]                       # cluster row of every surviving instance
+            rep_rows = torch.from_numpy(reps[final_rows]).to(d['pdev'])
             bb_scores = d['bbs'][rep_rows, 0]
-            if mode == 'eval':
-                results[d['name']] = {'conf': bb_scores, 'label_id': instance_labels, 'mask': out.bool().to(pdev)}
-            else:
+            results[d['name']] = {'conf': bb_scores, 'label_id': instance_labels, 'mask': out.bool().to(d['pdev'])}
+            if mode != 'eval':
                 fr = torch.from_numpy(final_rows).to(dev)
                 heat_w_bg = torch.zeros((kk, d['fg_dev'].shape[0]), device=dev)
                 heat_w_bg[:, d['fg_dev']] = r.heat[fr]
-                results[d['name']] = {
-                    'conf': bb_scores, 'label_id': instance_labels, 'mask': out.bool().to(pdev),
+                results[d['name']].update({
                     'cluster_representatives': rep_rows,
-                    'cluster_heatmaps': heat_w_bg[:, d['s2v']].to(pdev),
+                    'cluster_heatmaps': heat_w_bg[:, d['s2v']].to(d['pdev']),
                     'bbs': d['bbs'][rep_rows],
                     'pred_fg': d['fg'],
-                }
+                })
         return results
 
     def detection2mask_sweep(self, batch, pred, cfg, grid, gt_ids, acc=None):

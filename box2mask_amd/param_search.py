@@ -23,7 +23,8 @@ So 600 settings cost 6 clusterings and 24 mask stages per batch, a few host read
 has no mask NMS to sweep.
 
 The reference's search is not ScanNet-specific: with ``dataset_name = arkitscenes`` every job ends in ``arkitscenes_eval``
-(evaluation.py:245-316), the oriented-box detection mAP.  The front half above is shared (``_cluster_stages``); what a stage is
+(evaluation.py:245-316), the oriented-box detection mAP.  The front half above is shared (``_cluster_stages``, built on the scene
+inputs, the clustering read-back and the ``MaskTable`` of mask_stages.py, which ``detection2mask`` calls as well); what a stage is
 scored with differs:
 
   * per projected row its point count, z range and x-y convex hull, and the IoU of that prism with every same-class ground-truth
@@ -33,7 +34,8 @@ scored with differs:
   * rows under 50 points are skipped AFTER the mask NMS (evaluation.py:280)          -> ``detection_records`` gates what ``compose`` kept.
 
 The S3DIS flow (per-voxel semantics head, no mask NMS; evaluation.py:124-231) is the third: ``s3dis_param_search`` scores mPrec / mRec.
-There the wall DBSCAN depends on no threshold (once per room), the greedy merge of the proposals is prefix-closed (one
+Its stage 0 and clustering are the same ``mask_stages`` functions, for a batch of one room.  There the wall DBSCAN depends on no
+threshold (once per room), the greedy merge of the proposals is prefix-closed (one
 ``b2m_paint_proposals`` per (cluster_th, mask_bin_th) over the rows of the smallest score_th) and ``b2m_s3dis_prefix_tail`` scores every
 score prefix of a stage at once; profiles/s3dis_sweep_rule.md has the rule.
 
@@ -54,7 +56,7 @@ from . import _lib
 from . import eval_detection
 from . import eval_metric
 from . import iou_nms
-from .util import to_bbs_min_max
+from . import mask_stages
 
 _call = _lib.call
 AXES = ('cluster_th', 'score_th', 'mask_bin_th', 'mask_nms_th')
@@ -125,59 +127,13 @@ def records(tables, ci, si, bi, mi):
 
 
 # ----------------------------------------------------------------------------------------------------------------- device stages
-def _scene_inputs(net, batch, pred, cfg, dev):
-    """Stage 0 of ``SelectionNet.detection2mask`` in the ScanNet flow: boxes of the foreground votes, their slots, the voxel labels."""
+def _scannet_inputs(net, batch, pred, cfg, dev):
+    """``mask_stages.scene_inputs`` with the points, for the sweeps of the ScanNet flow."""
     if net.requires_voxel_outputs:
         raise ValueError('this threshold sweep covers the ScanNet flow only (segment-level votes, mask NMS): a network with a '
                          'per-voxel semantics head (requires_voxel_outputs) has no mask NMS to sweep -- its thresholds are swept '
                          'with the S3DIS metric by param_search.s3dis_param_search')
-    pdev = pred[cfg.mlp_offsets].device
-    pred_bbs = to_bbs_min_max(batch['input_location'].to(pdev), pred[cfg.mlp_offsets], pred[cfg.mlp_bounds],
-                              torch.nn.Sigmoid()(pred[cfg.mlp_bb_scores]))
-    pred_semantics = torch.argmax(pred[cfg.mlp_semantics], 1)
-    pred_semantics = net.semantic_valid_class_ids.to(pdev)[pred_semantics].long()
-    batch_ids = batch['batch_ids'].to(pdev)
-    sc = []
-    for scene_idx, scene in enumerate(batch['scene']):
-        scene_mask = batch_ids == scene_idx
-        if cfg.do_segment_pooling:
-            seg2vox = torch.as_tensor(batch['seg2vox'][scene_idx]).long()
-        else:
-            seg2vox = torch.arange(int(scene_mask.sum()), dtype=torch.long)
-        n_vox = seg2vox.shape[0]
-        s2v = seg2vox.to(dev)
-        scene_sem = pred_semantics[scene_mask]
-        fg = net.is_foreground(scene_sem)
-        boxes = pred_bbs[scene_mask][fg].detach().to(dev, torch.float32).contiguous()
-        if boxes.shape[0] == 0:
-            raise ValueError('NMS_clustering needs at least one box (the reference raises on n == 0 as well)')
-        fg_dev = fg.to(dev)
-        fg_slot = torch.where(fg_dev, torch.cumsum(fg_dev.int(), 0) - 1, torch.full_like(fg_dev.int(), -1)).int()
-        v2p = torch.as_tensor(batch['vox2point'][scene_idx]).long().to(dev).contiguous()
-        sc.append(dict(name=scene['name'], idx=scene_idx, s2v=s2v, n_vox=n_vox, sem32=scene_sem.to(dev)[s2v].int().contiguous(),
-                       fg_slot=fg_slot, boxes=boxes, n_fg=int(boxes.shape[0]), words=(n_vox + 63) // 64, v2p=v2p,
-                       n_pts=int(v2p.shape[0]), pdev=pdev))
-    return sc
-
-
-def _cluster(sc, cluster_th, score_ths):
-    """Clusters of every scene for one cluster_th (one launch, two host reads for the batch): per scene the device result and
-    dict(K, conf, reps, ks)."""
-    rs = iou_nms.nmc_device_batch([d['boxes'] for d in sc], float(cluster_th))
-    rep_scores = torch.cat([d['boxes'][r.reps[:r.k].long(), 0] for d, r in zip(sc, rs)]).cpu().numpy()
-    reps_host = torch.cat([r.reps[:r.k] for r in rs]).cpu().numpy().astype(np.int64)
-    out, o = [], 0
-    for r in rs:
-        conf, reps = rep_scores[o:o + r.k], reps_host[o:o + r.k]
-        o += r.k
-        ks = np.zeros(len(score_ths), np.int64)
-        for si, th in enumerate(score_ths):
-            sel = np.nonzero(conf > np.float32(th))[0]                     # detection_net.py:427-432, as detection2mask filters
-            if not np.array_equal(sel, np.arange(len(sel))):
-                raise ValueError('the score filter did not keep a prefix of the clusters (NaN scores?)')
-            ks[si] = len(sel)
-        out.append(dict(K=int(r.k), conf=conf.copy(), reps=reps.copy(), ks=ks))
-    return rs, out
+    return mask_stages.scene_inputs(net, batch, pred, cfg, dev, points=True)
 
 
 def sweep_tables(net, batch, pred, cfg, grid, gt_ids, acc=None):
@@ -189,7 +145,7 @@ def sweep_tables(net, batch, pred, cfg, grid, gt_ids, acc=None):
     of the stage in one launch, and the tables come back with ``clusters`` only (``stages`` stay empty lists)."""
     _lib.require_gpu()
     dev = torch.device('cuda', torch.cuda.current_device())
-    sc = _scene_inputs(net, batch, pred, cfg, dev)
+    sc = _scannet_inputs(net, batch, pred, cfg, dev)
     if not sc:
         return []
     S = len(sc)
@@ -230,15 +186,15 @@ def sweep_tables(net, batch, pred, cfg, grid, gt_ids, acc=None):
 def _hist_tail(c, sc):
     """The scorer's part of a cluster stage for the ScanNet AP: the point histograms behind the labels, and the B2M_HIST_DESC table."""
     hdesc = np.zeros((len(sc), 10), np.int64)
-    tb_all = torch.empty(max(sum(d['n_vox'] * ((k + 63) // 64) for k, d in zip(c.ksels, sc)), 1), dtype=torch.int64, device=c.dev)
+    tb_all, tb_ptrs = mask_stages.voxel_major_scratch(sc, c.ksels, c.dev)
     n_hist = sum(k * d['G'] for k, d in zip(c.ksels, sc))
 
     def fill(res):
-        toff = hoff = 0
+        hoff = 0
         for s_, (d, k) in enumerate(zip(sc, c.ksels)):
             hdesc[s_] = (c.bits_ptr[s_], k, d['words'], d['n_vox'], d['v2p'].data_ptr(), d['dense32'].data_ptr(), d['n_pts'], d['G'],
-                         tb_all.data_ptr() + 8 * toff, res.data_ptr() + 4 * (c.o_tail + hoff))
-            toff += d['n_vox'] * ((k + 63) // 64); hoff += k * d['G']
+                         tb_ptrs[s_], res.data_ptr() + 4 * (c.o_tail + hoff))
+            hoff += k * d['G']
         return hdesc.reshape(-1), tb_all
     return n_hist, fill
 
@@ -267,47 +223,29 @@ def _cluster_stages(sc, grid, dev, tabs, n_class, tail):
     """The front half every scorer shares: per cluster_th the clustering, the prefixes ``ks`` (appended to ``tabs``) and a
     ``_ClusterStage``.  ``tail(c, sc)`` -> (number of int32 the scorer wants behind the labels, fill(res) -> (its int64 descriptor
     table, whatever must stay alive)): the table rides behind the B2M_MASK_DESC table in the one upload, at ``c.extra_ptr``."""
-    S = len(sc)
     ths_nms = np.ascontiguousarray(grid.mask_nms_th, np.float32)           # C float, as float(mask_nms_th) becomes at the ABI
     n_nms = len(ths_nms)
     max_words, max_pts = max(d['words'] for d in sc), max(d['n_pts'] for d in sc)
-    for cth in grid.cluster_th:
+    for ci, cth in enumerate(grid.cluster_th):
         c = _ClusterStage()
-        c.rs, c.cl = _cluster(sc, cth, grid.score_th)
+        found = mask_stages.clusters(sc, float(cth))
+        c.rs = [r for r, _, _ in found]
+        c.cl = [dict(K=int(r.k), conf=conf.copy(), reps=reps.copy(), ks=mask_stages.score_prefixes(conf, grid.score_th))
+                for r, conf, reps in found]
         for t, cl_ in zip(tabs, c.cl):
             t.clusters.append(cl_)
             t.stages.append([])
-        c.ci, c.dev, c.n_class, c.ths_nms, c.n_nms, c.max_words, c.max_pts = len(tabs[0].clusters) - 1, dev, n_class, ths_nms, n_nms, max_words, max_pts
+        c.ci, c.dev, c.n_class, c.ths_nms, c.n_nms, c.max_words, c.max_pts = ci, dev, n_class, ths_nms, n_nms, max_words, max_pts
         # rows no setting can keep are never projected: the prefix of the SMALLEST score_th (the grid is ascending)
-        ksels = c.ksels = [int(cl_['ks'][0]) for cl_ in c.cl]
-        total = c.total = sum(ksels)
-        sel_all = torch.cat([torch.arange(k, dtype=torch.int32) for k in ksels]).to(dev) if total else \
-            torch.zeros(1, dtype=torch.int32, device=dev)
-        bits_all = torch.empty(max(sum(k * max(d['words'], 1) for k, d in zip(ksels, sc)), 1), dtype=torch.int64, device=dev)
-        inter_all = torch.empty(max(sum(k * k for k in ksels), 1), dtype=torch.int32, device=dev)
+        c.table = tab = mask_stages.MaskTable(sc, [r.heat for r in c.rs], [np.arange(int(cl_['ks'][0])) for cl_ in c.cl], dev)
+        c.ksels, c.total, c.row0, c.bits_ptr = tab.ksels, tab.total, tab.row0, tab.bits_ptr
         # every result of a stage in ONE int32 buffer -- keep flags | labels | the scorer's tail -- and one host read of it
-        c.o_lab, c.o_tail = n_nms * total, n_nms * total + total
-        c.bits_ptr, c.row0 = [], []
-        row0 = boff = 0
-        for d, k in zip(sc, ksels):
-            c.bits_ptr.append(bits_all.data_ptr() + 8 * boff)
-            c.row0.append(row0)
-            row0 += k; boff += k * max(d['words'], 1)
+        c.o_lab, c.o_tail = n_nms * c.total, n_nms * c.total + c.total
         n_tail, fill = tail(c, sc)
-        res = c.res = torch.zeros(max(c.o_tail + n_tail, 1), dtype=torch.int32, device=dev)
-        desc = np.zeros((S, 20), np.int64)
-        ioff = 0
-        for s_, (d, r, k) in enumerate(zip(sc, c.rs, ksels)):
-            row0 = c.row0[s_]
-            desc[s_, 0:10] = (r.heat.data_ptr(), d['n_fg'], sel_all.data_ptr() + 4 * row0, k, d['fg_slot'].data_ptr(),
-                              d['s2v'].data_ptr(), d['n_vox'], c.bits_ptr[s_], d['words'], inter_all.data_ptr() + 4 * ioff)
-            desc[s_, 11:15] = (0, k, d['sem32'].data_ptr(), res.data_ptr() + 4 * (c.o_lab + row0))      # every projected row
-            desc[s_, 18:20] = (row0, row0)
-            ioff += k * k
-        extra, c.alive = fill(res)
-        tables_dev = c.tables_dev = torch.from_numpy(np.concatenate([desc.reshape(-1), extra])).to(dev)
-        c.desc_ptr, c.extra_ptr = tables_dev.data_ptr(), tables_dev.data_ptr() + 8 * S * 20
-        c.keep_alive = (sel_all, bits_all, inter_all)
+        c.res = torch.zeros(max(c.o_tail + n_tail, 1), dtype=torch.int32, device=dev)
+        tab.set_kept(c.ksels, 0, c.res.data_ptr() + 4 * c.o_lab)             # every projected row gets its label
+        extra, c.alive = fill(c.res)
+        c.desc_ptr, c.extra_ptr = tab.upload(extra)
         yield c
 
 
@@ -384,7 +322,7 @@ def detection_tables(net, batch, pred, cfg, grid, positions=None, labels=None, o
     hull beyond B2M_HULL_MAX vertices in a row some setting keeps raises B2MError."""
     _lib.require_gpu()
     dev = torch.device('cuda', torch.cuda.current_device())
-    sc = _scene_inputs(net, batch, pred, cfg, dev)
+    sc = _scannet_inputs(net, batch, pred, cfg, dev)
     if not sc:
         return []
     if cap < 64 or cap & (cap - 1):
@@ -480,9 +418,7 @@ def arkit_param_search(model, batches, grid, oriented_boxes=True, iou_t=0.5, per
         raise ValueError('iou_t: a threshold or a non-empty sequence of thresholds')
     recs = {st: {} for st in settings}
     keys = {st: [] for st in settings}
-    for item in batches:
-        batch, pred = item if isinstance(item, (tuple, list)) else \
-            (item, model.get_prediction(item, with_grad=False, to_cpu=True, min_size=True))
+    for batch, pred in _predicted(model, batches):
         for t in model.pred2mask_detection_sweep(batch, pred, grid, oriented_boxes=oriented_boxes):
             for st in settings:
                 recs[st][t.name] = detection_records(t, *st)
@@ -498,8 +434,7 @@ def arkit_param_search(model, batches, grid, oriented_boxes=True, iou_t=0.5, per
         aps, means = done[key]
         out_map[st] = means
         by_class[st] = tuple(aps) if many else aps[0]
-    rank = lambda st: -np.inf if np.isnan(out_map[st][0]) else out_map[st][0]
-    best = max(settings, key=lambda st: (rank(st), tuple(-i for i in st)))
+    best = _best(settings, lambda st: (out_map[st][0],))
     out = dict(map=out_map if many else out_map[..., 0], best=best, best_ths=grid.eval_ths(*best), n_evaluated=len(done))
     if per_class:
         out['ap_by_class'] = by_class
@@ -527,28 +462,45 @@ def materialize(net, batch, pred, cfg, grid, tables, ci, si, bi, mi):
     the chosen rows are projected and gathered again (for the tests, and for the masks of the winning setting)."""
     _lib.require_gpu()
     dev = torch.device('cuda', torch.cuda.current_device())
-    sc = _scene_inputs(net, batch, pred, cfg, dev)
+    sc = _scannet_inputs(net, batch, pred, cfg, dev)
     rs = iou_nms.nmc_device_batch([d['boxes'] for d in sc], float(grid.cluster_th[ci])) if sc else []
     by_name = {t.name: t for t in tables}
     out = {}
     for d, r in zip(sc, rs):
         t = by_name[d['name']]
         rows = compose(t, ci, si, bi, mi)
-        kk = len(rows)
         if r.k != t.clusters[ci]['K']:
             raise ValueError('%s: these tables were not made from this batch and these predictions' % d['name'])
-        sel = torch.from_numpy(rows.astype(np.int32)).to(dev)
-        bits = torch.empty((max(kk, 1), max(d['words'], 1)), dtype=torch.int64, device=dev)
-        mask = torch.empty((kk, d['n_pts']), dtype=torch.uint8, device=dev)
-        _call('b2m_mask_project', r.heat.data_ptr(), d['n_fg'], sel.data_ptr(), kk, d['fg_slot'].data_ptr(), d['s2v'].data_ptr(),
-              d['n_vox'], float(grid.mask_bin_th[bi]), bits.data_ptr(), d['words'])
-        _call('b2m_mask_gather', bits.data_ptr(), d['words'], None, kk, d['v2p'].data_ptr(), d['n_pts'], mask.data_ptr())
+        mask = mask_stages.project_gather(d, r.heat, torch.from_numpy(rows.astype(np.int32)).to(dev), len(rows), grid.mask_bin_th[bi])
         out[d['name']] = {'conf': torch.from_numpy(t.clusters[ci]['conf'][rows]).to(d['pdev']),
                           'label_id': t.stages[ci][bi]['label_id'][rows].astype('int32'), 'mask': mask.bool().to(d['pdev'])}
     return out
 
 
 # ----------------------------------------------------------------------------------------------------------------- the search
+def _predicted(model, batches, clock=contextlib.nullcontext):
+    """(batch, pred) of every item of ``batches``: a pair as it is, a batch dict predicted here (inside ``clock('forward')``)."""
+    for item in batches:
+        with clock('forward'):
+            pair = item if isinstance(item, (tuple, list)) else \
+                (item, model.get_prediction(item, with_grad=False, to_cpu=True, min_size=True))
+        yield pair
+
+
+def _best(settings, key):
+    """The setting with the largest ``key(st)`` (a tuple of figures, a NaN counts as -inf); ties go to the first in grid order."""
+    rank = lambda st: tuple(-np.inf if np.isnan(v) else v for v in key(st))
+    return max(settings, key=lambda st: (rank(st), tuple(-i for i in st)))
+
+
+def _averages(aps):
+    """(AP, AP50, AP25) of an ``evaluate_matches`` table through the unchanged ``eval_metric.compute_averages``."""
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)                     # (no class with ground truth: nanmean of nothing)
+        avg = eval_metric.compute_averages(aps)
+    return avg['all_ap'], avg['all_ap_50%'], avg['all_ap_25%']
+
+
 def scannet_param_search(model, batches, gt_ids_by_scene, grid, per_class=False, matching='host'):
     """Score every setting of ``grid`` with the ScanNet AP over all ``batches``.
 
@@ -570,9 +522,7 @@ def scannet_param_search(model, batches, gt_ids_by_scene, grid, per_class=False,
         return _search_device(model, batches, gt_ids_by_scene, grid, per_class, shape, settings)
     matches = {st: {} for st in settings}
     keys = {st: [] for st in settings}
-    for item in batches:
-        batch, pred = item if isinstance(item, (tuple, list)) else \
-            (item, model.get_prediction(item, with_grad=False, to_cpu=True, min_size=True))
+    for batch, pred in _predicted(model, batches):
         for t in model.pred2mask_sweep(batch, pred, grid, gt_ids_by_scene):
             for st in settings:
                 ci, si, bi, mi = st
@@ -586,16 +536,12 @@ def scannet_param_search(model, batches, gt_ids_by_scene, grid, per_class=False,
         key = tuple(keys[st])
         if key not in done:
             aps, _ = eval_metric.evaluate_matches(matches[st])
-            with warnings.catch_warnings():
-                warnings.simplefilter('ignore', RuntimeWarning)             # (no class with ground truth: nanmean of nothing)
-                avg = eval_metric.compute_averages(aps)
-            done[key] = (aps, (avg['all_ap'], avg['all_ap_50%'], avg['all_ap_25%']))
+            done[key] = (aps, _averages(aps))
         aps, three = done[key]
         ap[st] = three
         if per_class:
             ap_tables[st] = aps
-    rank = lambda st: tuple(-np.inf if np.isnan(v) else v for v in (ap[st][1], ap[st][0]))
-    best = max(settings, key=lambda st: (rank(st), tuple(-i for i in st)))
+    best = _best(settings, lambda st: (ap[st][1], ap[st][0]))
     out = dict(ap=ap, best=best, best_ths=grid.eval_ths(*best), n_evaluated=len(done))
     if per_class:
         out['ap_tables'] = ap_tables
@@ -605,19 +551,13 @@ def scannet_param_search(model, batches, gt_ids_by_scene, grid, per_class=False,
 def _search_device(model, batches, gt_ids_by_scene, grid, per_class, shape, settings):
     from . import eval_match
     acc = eval_match.MatchAccumulator(len(settings))
-    for item in batches:
-        batch, pred = item if isinstance(item, (tuple, list)) else \
-            (item, model.get_prediction(item, with_grad=False, to_cpu=True, min_size=True))
+    for batch, pred in _predicted(model, batches):
         model.pred2mask_sweep(batch, pred, grid, gt_ids_by_scene, acc=acc)
     table = acc.finish()                                                   # (settings, classes, overlaps), grid order
     ap = np.full(shape + (3,), np.nan)
     for q, st in enumerate(settings):
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore', RuntimeWarning)
-            avg = eval_metric.compute_averages(table[q:q + 1])
-        ap[st] = (avg['all_ap'], avg['all_ap_50%'], avg['all_ap_25%'])
-    rank = lambda st: tuple(-np.inf if np.isnan(v) else v for v in (ap[st][1], ap[st][0]))
-    best = max(settings, key=lambda st: (rank(st), tuple(-i for i in st)))
+        ap[st] = _averages(table[q:q + 1])
+    best = _best(settings, lambda st: (ap[st][1], ap[st][0]))
     out = dict(ap=ap, best=best, best_ths=grid.eval_ths(*best), n_evaluated=len(settings))
     if per_class:
         out['ap_tables'] = table.reshape(shape + (len(eval_metric.CLASS_LABELS), len(eval_metric.OVERLAPS)))[..., None, :, :].copy()
@@ -643,38 +583,14 @@ class S3DISSweepResult(dict):
 
 
 def _s3dis_room(net, batch, pred, cfg, dev):
-    """Stage 0 of ``SelectionNet.detection2mask`` in the S3DIS flow (detection_net.py:398-415) for a batch of ONE room: the boxes
-    of the segments whose voxels vote a foreground class, their slots, and the predicted class of every point."""
-    from .eval_s3dis import NUM_CLASSES
+    """``mask_stages.scene_inputs`` with the points for a batch of ONE room of the S3DIS flow: the boxes of the segments whose voxels
+    vote a foreground class, their slots, and the predicted class of every point (``sem_pts``)."""
     if not net.requires_voxel_outputs or cfg.mlp_per_vox_semantics not in cfg.network_heads:
         raise ValueError('s3dis_param_search needs the per-voxel semantics head (%s); the ScanNet / ARKitScenes flows are swept by '
                          'scannet_param_search / arkit_param_search' % cfg.mlp_per_vox_semantics)
     if len(batch['scene']) != 1:
         raise ValueError('S3DIS is evaluated with batch size 1 (evaluation.py:131)')
-    pdev = pred[cfg.mlp_offsets].device
-    pred_bbs = to_bbs_min_max(batch['input_location'].to(pdev), pred[cfg.mlp_offsets], pred[cfg.mlp_bounds],
-                              torch.nn.Sigmoid()(pred[cfg.mlp_bb_scores]))
-    sem_vox = torch.argmax(torch.as_tensor(pred[cfg.mlp_per_vox_semantics]), 1).to(dev).int().contiguous()
-    if cfg.do_segment_pooling:
-        s2v = torch.as_tensor(batch['seg2vox'][0]).long().to(dev).contiguous()
-    else:
-        s2v = torch.arange(sem_vox.shape[0], dtype=torch.long, device=dev)
-    n_vox = int(s2v.shape[0])
-    if sem_vox.shape[0] != n_vox:
-        raise ValueError('%d per-voxel predictions for %d voxels' % (sem_vox.shape[0], n_vox))
-    n_seg = int(pred_bbs.shape[0])
-    # torch.mode per segment (detection_net.py:399-409): the lowest class on ties
-    hist = torch.empty(max(n_seg * NUM_CLASSES, 1), dtype=torch.int32, device=dev)
-    mode = torch.zeros(max(n_seg, 1), dtype=torch.int32, device=dev)
-    _call('b2m_seg_mode', s2v.int().contiguous().data_ptr(), sem_vox.data_ptr(), n_vox, n_seg, NUM_CLASSES, hist.data_ptr(), mode.data_ptr())
-    fg_dev = net.is_foreground(mode[:n_seg])
-    boxes = pred_bbs.detach().to(dev, torch.float32)[fg_dev].contiguous()
-    if boxes.shape[0] == 0:
-        raise ValueError('NMS_clustering needs at least one box (the reference raises on n == 0 as well)')
-    fg_slot = torch.where(fg_dev, torch.cumsum(fg_dev.int(), 0) - 1, torch.full_like(fg_dev.int(), -1)).int()
-    v2p = torch.as_tensor(np.asarray(batch['vox2point'][0])).long().to(dev).contiguous()
-    return dict(name=batch['scene'][0]['name'], idx=0, s2v=s2v, n_vox=n_vox, fg_slot=fg_slot, boxes=boxes, n_fg=int(boxes.shape[0]),
-                words=(n_vox + 63) // 64, v2p=v2p, n_pts=int(v2p.shape[0]), sem_pts=sem_vox[v2p].contiguous())
+    return mask_stages.scene_inputs(net, batch, pred, cfg, dev, points=True)[0]
 
 
 def s3dis_stage(d, r, k_rows, mask_bin_th, clock=contextlib.nullcontext):
@@ -687,15 +603,10 @@ def s3dis_stage(d, r, k_rows, mask_bin_th, clock=contextlib.nullcontext):
     n = d['n_pts']
     pwords = (n + 63) // 64
     with clock('projection'):
-        sel = torch.arange(max(k_rows, 1), dtype=torch.int32, device=dev)
-        bits = torch.empty((max(k_rows, 1), max(d['words'], 1)), dtype=torch.int64, device=dev)
-        masks = torch.empty((k_rows, n), dtype=torch.uint8, device=dev)
+        masks = mask_stages.project_gather(d, r.heat, torch.arange(max(k_rows, 1), dtype=torch.int32, device=dev), k_rows, mask_bin_th)
         pbits = torch.empty((max(k_rows, 1), max(pwords, 1)), dtype=torch.int64, device=dev)
         prop_sem = torch.zeros(max(k_rows, 1), dtype=torch.int32, device=dev)
         if k_rows:
-            _call('b2m_mask_project', r.heat.data_ptr(), d['n_fg'], sel.data_ptr(), k_rows, d['fg_slot'].data_ptr(), d['s2v'].data_ptr(),
-                  d['n_vox'], float(mask_bin_th), bits.data_ptr(), d['words'])
-            _call('b2m_mask_gather', bits.data_ptr(), d['words'], None, k_rows, d['v2p'].data_ptr(), n, masks.data_ptr())
             _call('b2m_mask_pack', masks.data_ptr(), k_rows, n, pbits.data_ptr(), pwords)
             _call('b2m_label_hist', pbits.data_ptr(), pwords, None, k_rows, d['sem_pts'].data_ptr(), n, S.NUM_CLASSES, prop_sem.data_ptr())
     with clock('paint'):
@@ -753,29 +664,18 @@ def _s3dis_ground_truth(labels, dev):
     return gi, gt_class, gt_size, torch.bincount(gt_class.long(), minlength=S.NUM_CLASSES)[:S.NUM_CLASSES]
 
 
-class _StageClock:
+def _stage_clock(timing):
     """clock(name): a context manager that adds the device milliseconds of its body to ``timing[name]`` (HIP events; it waits for
     the second one, so a timed search is a pass of its own)."""
-
-    def __init__(self, timing):
-        self.timing = timing
-
-    def __call__(self, name):
-        return _StageSpan(self.timing, name)
-
-
-class _StageSpan:
-    def __init__(self, timing, name):
-        self.timing, self.name = timing, name
-
-    def __enter__(self):
-        self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        self.a.record()
-
-    def __exit__(self, *exc):
-        self.b.record()
-        self.b.synchronize()
-        self.timing[self.name] = self.timing.get(self.name, 0.0) + self.a.elapsed_time(self.b)
+    @contextlib.contextmanager
+    def clock(name):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        yield
+        b.record()
+        b.synchronize()
+        timing[name] = timing.get(name, 0.0) + a.elapsed_time(b)
+    return clock
 
 
 def s3dis_param_search(model, batches, grid, full_rooms=None, per_class=False, timing=None):
@@ -810,11 +710,8 @@ def s3dis_param_search(model, batches, grid, full_rooms=None, per_class=False, t
     fp = torch.zeros_like(tp)
     total_gt = torch.zeros(S.NUM_CLASSES, dtype=torch.int64, device=dev)
 
-    clock = _StageClock(timing) if timing is not None else contextlib.nullcontext
-    for i, item in enumerate(batches):
-        with clock('forward'):
-            batch, pred = item if isinstance(item, (tuple, list)) else \
-                (item, model.get_prediction(item, with_grad=False, to_cpu=True, min_size=True))
+    clock = _stage_clock(timing) if timing is not None else contextlib.nullcontext
+    for i, (batch, pred) in enumerate(_predicted(model, batches, clock)):
         d = _s3dis_room(net, batch, pred, cfg, dev)
         scene, labels = batch['scene'][0], batch['labels'][0]
         with clock('dbscan'):
@@ -831,11 +728,11 @@ def s3dis_param_search(model, batches, grid, full_rooms=None, per_class=False, t
         bg_top = int(bg.max().item()) if d['n_pts'] else 0
         for ci, cth in enumerate(grid.cluster_th):
             with clock('clustering'):
-                rs, cl = _cluster([d], cth, grid.score_th)
-            ks = cl[0]['ks']
+                (r, conf, _), = mask_stages.clusters([d], float(cth))
+            ks = mask_stages.score_prefixes(conf, grid.score_th)
             k_rows = int(ks[0])
             for bi, bth in enumerate(grid.mask_bin_th):
-                owner, prop_sem, _, _ = s3dis_stage(d, rs[0], k_rows, bth, clock=clock)
+                owner, prop_sem, _, _ = s3dis_stage(d, r, k_rows, bth, clock=clock)
                 with clock('tail'):
                     s3dis_prefix_tail(owner, prop_sem, bg, d['sem_pts'], ks, k_rows + max(bg_top, 0) + 1, gi, gt_class, gt_size, tp[ci, bi],
                                       fp[ci, bi], index=index)

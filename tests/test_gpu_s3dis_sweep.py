@@ -200,6 +200,7 @@ def test_search_equals_the_reference(fx, sweep):
 def test_stage_labels_equal_the_reference(fx, model, items, grid):
     """The labels of every setting, from the shared stage and the kernel: instances and semantics of the 36 x 2 reference rooms."""
     from box2mask_amd import eval_s3dis as S
+    from box2mask_amd import mask_stages as M
     from box2mask_amd import param_search as P
     z = fx['z']
     dev = torch.device('cuda')
@@ -214,11 +215,11 @@ def test_stage_labels_equal_the_reference(fx, model, items, grid):
         want_gi, want_cls = R.gt_tables(rm['gt_ins'], rm['gt_sem'])
         assert np.array_equal(gi.cpu().numpy(), want_gi) and np.array_equal(gt_class.cpu().numpy(), want_cls)
         for ci, cth in enumerate(grid.cluster_th):
-            rs, cl = P._cluster([d], cth, grid.score_th)
+            (r0, conf, _), = M.clusters([d], float(cth))
             for bi, bth in enumerate(grid.mask_bin_th):
-                ks = cl[0]['ks']
+                ks = M.score_prefixes(conf, grid.score_th)
                 assert np.array_equal(ks, rm['k'][ci, :, bi])
-                owner, prop_sem, accepted, masks = P.s3dis_stage(d, rs[0], int(ks[0]), bth)
+                owner, prop_sem, accepted, masks = P.s3dis_stage(d, r0, int(ks[0]), bth)
                 assert np.array_equal(masks.cpu().numpy().astype(bool), rm['stage_masks'][(ci, bi)])
                 want_owner, want_sem, fate = R.paint(rm['stage_masks'][(ci, bi)], rm['sem'])
                 assert np.array_equal(owner.cpu().numpy(), want_owner) and np.array_equal(prop_sem.cpu().numpy(), want_sem)
