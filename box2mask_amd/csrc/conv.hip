@@ -1477,7 +1477,7 @@ struct WgradArgs {
     int kpack;                // offsets per workgroup: 1, or -- layers with only 1 or 2 (ci, co) blocks -- 4 or 2: the waves
                               // a single block would leave idle take the neighbouring offsets of the same tile chunk
     int kgroups;              // ceil(K / kpack)
-    int handloads;            // conv_wgrad_flow_kernel<.., HL = 1> (B2M_WGRAD_HANDLOADS)
+    int handloads;            // conv_wgrad_flow_kernel<.., LOADS = 1> (B2M_WGRAD_HANDLOADS)
     int swap;                 // b2m_conv_wgrad_tr: x is indexed by the tile's own rows (row0 + rb_out), dy by rb_in
     int half;                 // b2m_conv_wgrad_h: x and dy are IEEE binary16 (pitches in elements), converted on load; fp32 MFMA, fp32 dW
     float out_scale;          // ... and the block is multiplied by this on its way into dW (1 / loss scale)
@@ -1516,6 +1516,22 @@ __device__ __forceinline__ bool wgrad_item(const WgradArgs& a, int wave, int& k,
     }
     return true;
 }
+// flat walk of a wave over the non-empty 16-pair slots of its tiles (conv_wgrad_flow_kernel, conv_wgrad_trh_kernel): position =
+// (tile index ti, group g); lane t holds the pair count of tile t0 + t, `live` has the bits of the tiles with pairs
+struct WgradWalk {
+    int cnt; uint64_t live;
+    __device__ __forceinline__ int pairs_of(int ti, int g) const {
+        const int n = __builtin_amdgcn_readlane(cnt, ti) - 16 * g;
+        return n > 16 ? 16 : n;
+    }
+    __device__ __forceinline__ bool advance(int& ti, int& g) const {      // false past the end
+        if (16 * (g + 1) < __builtin_amdgcn_readlane(cnt, ti)) { ++g; return true; }
+        const uint64_t rest_mask = ti >= 63 ? 0ull : (live >> (ti + 1));
+        if (rest_mask == 0) return false;
+        ti = ti + 1 + __builtin_ctzll(rest_mask); g = 0;
+        return true;
+    }
+};
 
 // H = 1 (b2m_conv_wgrad_h, half-precision training): the operands are binary16 in memory -- half the gathered bytes --, every
 // element is converted as it is loaded, and the block is accumulated by the same fp32 MFMAs (the f16 MFMA wants four PAIRS per
@@ -1657,7 +1673,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, int nchun
     }
 }
 
-// Hand-issued loads of conv_wgrad_flow_kernel<MI, NJ, HL != 0>: the two asm statements of a k-step, composed per block shape
+// Hand-issued loads of conv_wgrad_flow_kernel<MI, NJ, LOADS = 1>: the two asm statements of a k-step, composed per block shape
 // (MI, NJ in 2..4) from named operands.  WG_GATHER: the MI + NJ operand loads inside ONE EXEC window (destinations are in/out
 // operands, see the kernel); WG_SELECT: the counted wait and the moves (0 for a missing pair) into the MFMA operands.
 #define WG_LA2 "global_load_dword %[a0], %[bx], %[px]\n\tglobal_load_dword %[a1], %[bx], %[px] offset:64\n\t"
@@ -1717,7 +1733,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, int nchun
 //    accumulators in AGPRs and copied all of them to VGPRs and back around every slot (108 moves per 36 MFMAs);
 //  * each slot issues the same number of loads (k-steps without pairs gather row 0: L1 hits), so the counted waits
 //    in front of the MFMAs are exact; the loads that refill a k-step's registers follow its MFMAs directly.
-// HL = 1 (round 4; real rulebooks, blocks of 2..4 x 2..4 sub-tiles): the operand and pair-list loads are issued by hand, as in
+// LOADS = 1 (HL; round 4; real rulebooks, blocks of 2..4 x 2..4 sub-tiles): the operand and pair-list loads are issued by hand, as in
 // conv_fwd_flow_kernel -- a k-step's MI + NJ loads sit in ONE EXEC window that holds the lanes whose pair exists (a slot's
 // missing pairs and empty k-steps fetch nothing: 14 % of the loads on the benchmark's maps), the waits are counted here: the
 // operands of k-step s are complete when all but the 3 (MI + NJ) refills and the 2 list loads issued since have landed.
@@ -1729,9 +1745,18 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, int nchun
 //    flight: the next address computation landed in it, a GPU memory fault).
 // SWP = 1 (round 5, b2m_conv_wgrad_tr): x lives on the tile's rows, dy on the rows the pair list names -- a variant of its own: as a
 // run-time switch the select cost the 2 x 4 blocks a resident wave (81 VGPRs)
-template <int MI, int NJ, int HL = 0, int SWP = 0>
+// LOADS = 2 (round 6, b2m_conv_wgrad_h: half-precision training): the operands are IEEE binary16, hipcc-tracked loads only.  A load
+// brings the 16 bits of its element into a 32-bit register, the conversion to fp32 sits in front of the k-step's MFMAs, one slot
+// after the load; the slots and the fp32 MFMAs are those of the fp32 form, the gathered bytes half.
+// The half form is a value of a template parameter of THIS kernel, not a second kernel around a shared body: a forced-inline device
+// function under two __global__ wrappers (arguments by reference or by value) made hipcc schedule every flow kernel differently,
+// `if constexpr` on a parameter leaves each instantiation's instructions as they were (profiles/wgrad_fold_refactor.md).
+template <int MI, int NJ, int LOADS = 0, int SWP = 0>      // LOADS: 0 = fp32, tracked by hipcc; 1 = fp32, hand-issued; 2 = binary16, tracked
 __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
+    constexpr int HL = (LOADS == 1), H = (LOADS == 2);
+    static_assert(LOADS >= 0 && LOADS <= 2, "load mode: 0, 1 or 2 (hand-issued loads exist for fp32 operands only)");
     static_assert(!HL || (MI >= 2 && NJ >= 2), "hand-issued loads: blocks of 2..4 x 2..4 sub-tiles");
+    constexpr uint32_t ESZ = H ? 2u : 4u;      // bytes per operand element
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 15, q = lane >> 4;
@@ -1752,15 +1777,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
     const uint64_t live = __ballot(cnt > 0);
     if (live == 0) return;
 
-    // flat walk: position = (tile index ti, group g); advance() returns false past the end
-    auto pairs_of = [&](int ti, int g) { const int n = __builtin_amdgcn_readlane(cnt, ti) - 16 * g; return n > 16 ? 16 : n; };
-    auto advance = [&](int& ti, int& g) {
-        if (16 * (g + 1) < __builtin_amdgcn_readlane(cnt, ti)) { ++g; return true; }
-        const uint64_t rest_mask = ti >= 63 ? 0ull : (live >> (ti + 1));
-        if (rest_mask == 0) return false;
-        ti = ti + 1 + __builtin_ctzll(rest_mask); g = 0;
-        return true;
-    };
+    const WgradWalk walk{cnt, live};
     const int64_t kbase = (int64_t)k * ldr + t0 * B2M_TILE;
     // list of a slot: lane (i, .) loads entry i; word = input row | row inside the tile << 24, bit 31 = no pair
     auto load_list = [&](int ti, int g, int& r_in, int& r_out) {
@@ -1789,9 +1806,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) w[s] = (uint32_t)__builtin_amdgcn_ds_bpermute((4 * s + q) << 2, (int)word);
     };
-    const uint32_t ldx4 = (uint32_t)a.ldx * 4u, lddy4 = (uint32_t)a.lddy * 4u;
-    const uint32_t cxb = (uint32_t)(ci0 + i) * 4u, cyb = (uint32_t)(co0 + i) * 4u;
-    float av[4][MI], bv[4][NJ];
+    const uint32_t ldx4 = (uint32_t)a.ldx * ESZ, lddy4 = (uint32_t)a.lddy * ESZ;
+    const uint32_t cxb = (uint32_t)(ci0 + i) * ESZ, cyb = (uint32_t)(co0 + i) * ESZ;
+    std::conditional_t<H != 0, uint32_t, float> av[4][MI], bv[4][NJ];      // (half: the 16 bits of a loaded element, zero-extended)
     if constexpr (HL != 0) {
         // hand-issued loads take their destination as an IN/OUT operand: the previous content stays alive, in that register, up to
         // the load.  (As a plain output the register is dead to hipcc from its last use on -- and the last use, the wait of a
@@ -1816,6 +1833,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
             // lanes whose pair exists (bit 31 of the word clear); at least lane 0, so that the loads are always issued
             const uint64_t em = __ballot((int)word >= 0) | 1ull;
             WG_DISPATCH(WG_GATHER)
+        } else if constexpr (H) {
+#pragma unroll
+            for (int m = 0; m < MI; ++m) av[s][m] = (uint32_t)*(const unsigned short*)(px + 32 * m);
+#pragma unroll
+            for (int nn = 0; nn < NJ; ++nn) bv[s][nn] = (uint32_t)*(const unsigned short*)(py + 32 * nn);
         } else {
 #pragma unroll
             for (int m = 0; m < MI; ++m) av[s][m] = *(const float*)(px + 64 * m);
@@ -1834,7 +1856,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
     uint32_t wC[4], wN[4];
     int rawi = 0, rawo = 0;
     int tiN = tiC, gN = gC;
-    bool hasN = advance(tiN, gN);
+    bool hasN = walk.advance(tiN, gN);
     {
         int r0i, r0o, r1i, r1o;
         load_list(tiC, gC, r0i, r0o);
@@ -1845,14 +1867,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) gather(s, tiC, wC[s]);
     int tiNN = tiN, gNN = gN;
-    bool hasNN = hasN && advance(tiNN, gNN);
+    bool hasNN = hasN && walk.advance(tiNN, gNN);
     if (HL) load_list_hl(hasNN ? tiNN : tiN, hasNN ? gNN : gN, rawi, rawo);
     else load_list(hasNN ? tiNN : tiN, hasNN ? gNN : gN, rawi, rawo);
     if (!hasN) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) wN[s] = 0x80000000u;       // no next slot: the refills gather row 0 and are never used
     }
-    int nkC = (pairs_of(tiC, gC) + 3) >> 2;
+    int nkC = (walk.pairs_of(tiC, gC) + 3) >> 2;
 
     for (;;) {
 #pragma unroll
@@ -1865,6 +1887,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
                     // it: as in/out operands of a bare wait, hipcc copied them to fresh registers IN FRONT of the wait.
                     const uint64_t pm = __ballot((int)wC[s] >= 0);
                     WG_DISPATCH(WG_SELECT)
+                } else if constexpr (H) {
+#pragma unroll
+                    for (int nn = 0; nn < NJ; ++nn)
+                        bz[nn] = (int)wC[s] >= 0 ? (float)__builtin_bit_cast(_Float16, (unsigned short)bv[s][nn]) : 0.f;
+#pragma unroll
+                    for (int m = 0; m < MI; ++m) az[m] = (float)__builtin_bit_cast(_Float16, (unsigned short)av[s][m]);
                 } else {
 #pragma unroll
                     for (int nn = 0; nn < NJ; ++nn) bz[nn] = (int)wC[s] >= 0 ? bv[s][nn] : 0.f;      // no pair: contributes 0
@@ -1898,7 +1926,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
         if (!hasN) break;
         // next slot becomes current; its successor's list has arrived; fetch one more
         tiC = tiN; gC = gN;
-        nkC = (pairs_of(tiC, gC) + 3) >> 2;
+        nkC = (walk.pairs_of(tiC, gC) + 3) >> 2;
 #pragma unroll
         for (int s = 0; s < 4; ++s) wC[s] = wN[s];
         hasN = hasNN; tiN = tiNN; gN = gNN;
@@ -1913,7 +1941,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) wN[s] = 0x80000000u;
         }
-        hasNN = hasN && advance(tiNN, gNN);
+        hasNN = hasN && walk.advance(tiNN, gNN);
         if (HL) load_list_hl(hasNN ? tiNN : tiN, hasNN ? gNN : gN, rawi, rawo);
         else load_list(hasNN ? tiNN : tiN, hasNN ? gNN : gN, rawi, rawo);
     }
@@ -1928,191 +1956,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_flow_kernel(WgradArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int ci = ci0 + 16 * m + 4 * q + r, co = co0 + 16 * nn + i;
                 if (ci < a.cin && co < a.cout) {
-                    const float v = acc[m][nn][r];
-                    if (v != 0.f) atomicAdd(&a.dw[(int64_t)k * a.dw_kstride + (int64_t)ci * a.lddw + co], v);
-                }
-            }
-    B2M_CLOCK_END(3);
-}
-// The same walk for IEEE binary16 operands (round 6, b2m_conv_wgrad_h: half-precision training) -- a kernel of its own, not a
-// variant of the template above: sharing the body through a forced-inline function changed hipcc's schedule of the fp32
-// kernels with 1 x 2 / 2 x 2 blocks and their weight gradients came out wrong (tests/test_gpu_conv_regimes.py caught it).
-// hipcc-tracked loads only: a load brings the 16 bits of its element into a 32-bit register, the conversion to fp32 sits in front
-// of the k-step's MFMAs, one slot after the load; the slots and the fp32 MFMAs are those of the fp32 kernel, the gathered bytes half.
-template <int MI, int NJ, int SWP>
-__global__ __launch_bounds__(256) void conv_wgrad_flow_h_kernel(WgradArgs a) {
-    constexpr int HL = 0;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i = lane & 15, q = lane >> 4;
-    int k, blk;
-    int64_t chunk, t0, t1;
-    if (!wgrad_item(a, wave, k, blk, chunk, t0, t1)) return;
-    B2M_CLOCK_BEGIN();
-    const int ci0 = (blk / a.nnb) * 16 * MI, co0 = (blk % a.nnb) * 16 * NJ;
-    const int64_t ldr = a.ntiles * B2M_TILE;
-    const int nt = (int)(t1 - t0);                       // <= 64 tiles: lane t holds the pair count of tile t0 + t
-    // identity map (1x1 layers): pair j of a tile is (row j, row j); never with hand-issued loads
-    const bool ident = HL ? false : a.rb_in == nullptr;
-    int cnt = 0;
-    if (lane < nt) {
-        if (ident) { const int64_t rem = a.n_out - (t0 + lane) * B2M_TILE; cnt = rem < B2M_TILE ? (int)rem : B2M_TILE; }
-        else cnt = a.rb_cnt[(int64_t)k * a.ntiles + t0 + lane];
-    }
-    const uint64_t live = __ballot(cnt > 0);
-    if (live == 0) return;
-
-    // flat walk: position = (tile index ti, group g); advance() returns false past the end
-    auto pairs_of = [&](int ti, int g) { const int n = __builtin_amdgcn_readlane(cnt, ti) - 16 * g; return n > 16 ? 16 : n; };
-    auto advance = [&](int& ti, int& g) {
-        if (16 * (g + 1) < __builtin_amdgcn_readlane(cnt, ti)) { ++g; return true; }
-        const uint64_t rest_mask = ti >= 63 ? 0ull : (live >> (ti + 1));
-        if (rest_mask == 0) return false;
-        ti = ti + 1 + __builtin_ctzll(rest_mask); g = 0;
-        return true;
-    };
-    const int64_t kbase = (int64_t)k * ldr + t0 * B2M_TILE;
-    // list of a slot: lane (i, .) loads entry i; word = input row | row inside the tile << 24, bit 31 = no pair
-    auto load_list = [&](int ti, int g, int& r_in, int& r_out) {
-        if (ident) {                                     // (wave-uniform)
-            const int64_t row = (t0 + ti) * B2M_TILE + 16 * g + i;
-            r_in = row < a.n_out ? (int)row : -1;
-            r_out = 16 * g + i;
-            return;
-        }
-        const int64_t base = kbase + (int64_t)ti * B2M_TILE + 16 * g + i;
-        r_in = a.rb_in[base];
-        r_out = a.rb_out[base];
-    };
-    auto load_list_hl = [&](int ti, int g, int& r_in, int& r_out) {      // (hand-issued)
-        const int64_t base = kbase + (int64_t)ti * B2M_TILE + 16 * g;      // wave-uniform
-        const int32_t* pin = a.rb_in + base;
-        const uint8_t* pout = a.rb_out + base;
-        // (destinations as IN/OUT operands, like the operand loads: the registers stay allocated up to the statement that
-        // waits for them, whatever hipcc moves in between)
-        asm volatile("global_load_dword %0, %1, %2" : "+v"(r_in) : "v"((uint32_t)i * 4u), "s"(pin) : "memory");
-        asm volatile("global_load_ubyte %0, %1, %2" : "+v"(r_out) : "v"((uint32_t)i), "s"(pout) : "memory");
-    };
-    // the word of pair 4s + q for k-step s
-    auto words = [&](int r_in, int r_out, uint32_t (&w)[4]) {
-        const uint32_t word = r_in < 0 ? 0x80000000u : ((uint32_t)r_in | ((uint32_t)r_out << 24));
-#pragma unroll
-        for (int s = 0; s < 4; ++s) w[s] = (uint32_t)__builtin_amdgcn_ds_bpermute((4 * s + q) << 2, (int)word);
-    };
-    const uint32_t ldx4 = (uint32_t)a.ldx * 2u, lddy4 = (uint32_t)a.lddy * 2u;
-    const uint32_t cxb = (uint32_t)(ci0 + i) * 2u, cyb = (uint32_t)(co0 + i) * 2u;
-    uint32_t av[4][MI], bv[4][NJ];          // (the 16 bits of a loaded element, zero-extended)
-    // operands of k-step s of the slot in tile ti (MI + NJ loads, always)
-    auto gather = [&](int s, int ti, uint32_t word) {
-        const uint32_t row0 = (uint32_t)((t0 + ti) * B2M_TILE);
-        const uint32_t rlist = word & 0xFFFFFFu, rtile = row0 + ((word >> 24) & 63u);
-        const uint32_t bx = __umul24(SWP ? rtile : rlist, ldx4) + cxb;
-        const uint32_t by = __umul24(SWP ? rlist : rtile, lddy4) + cyb;
-        const char* px = (const char*)a.x + bx;
-        const char* py = (const char*)a.dy + by;
-        {
-#pragma unroll
-            for (int m = 0; m < MI; ++m) av[s][m] = (uint32_t)*(const unsigned short*)(px + 32 * m);
-#pragma unroll
-            for (int nn = 0; nn < NJ; ++nn) bv[s][nn] = (uint32_t)*(const unsigned short*)(py + 32 * nn);
-        }
-    };
-    f32x4 acc[MI][NJ];
-#pragma unroll
-    for (int m = 0; m < MI; ++m)
-#pragma unroll
-        for (int n = 0; n < NJ; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // prologue: list + operands of slot 0, list of slot 1, list load of slot 2
-    int tiC = __builtin_ctzll(live), gC = 0;
-    uint32_t wC[4], wN[4];
-    int rawi = 0, rawo = 0;
-    int tiN = tiC, gN = gC;
-    bool hasN = advance(tiN, gN);
-    {
-        int r0i, r0o, r1i, r1o;
-        load_list(tiC, gC, r0i, r0o);
-        load_list(hasN ? tiN : tiC, hasN ? gN : gC, r1i, r1o);
-        words(r0i, r0o, wC);
-        words(r1i, r1o, wN);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) gather(s, tiC, wC[s]);
-    int tiNN = tiN, gNN = gN;
-    bool hasNN = hasN && advance(tiNN, gNN);
-    if (HL) load_list_hl(hasNN ? tiNN : tiN, hasNN ? gNN : gN, rawi, rawo);
-    else load_list(hasNN ? tiNN : tiN, hasNN ? gNN : gN, rawi, rawo);
-    if (!hasN) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) wN[s] = 0x80000000u;       // no next slot: the refills gather row 0 and are never used
-    }
-    int nkC = (pairs_of(tiC, gC) + 3) >> 2;
-
-    for (;;) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            if (s < nkC) {                                       // wave-uniform
-                float bz[NJ], az[MI];
-                {
-#pragma unroll
-                    for (int nn = 0; nn < NJ; ++nn)
-                        bz[nn] = (int)wC[s] >= 0 ? (float)__builtin_bit_cast(_Float16, (unsigned short)bv[s][nn]) : 0.f;
-#pragma unroll
-                    for (int m = 0; m < MI; ++m) az[m] = (float)__builtin_bit_cast(_Float16, (unsigned short)av[s][m]);
-                }
-#pragma unroll
-                for (int m = 0; m < MI; ++m)
-#pragma unroll
-                    for (int nn = 0; nn < NJ; ++nn)
-#ifdef B2M_WGRAD_NOMFMA      // diagnostic build (wrong results): what the loop costs without its MFMAs -- the operands stay consumed
-                        asm volatile("" : "+v"(acc[m][nn]) : "v"(az[m]), "v"(bz[nn]));
-#else
-                    {
-                        // (VALU write -> MFMA operand: 2 wait states, see the fp32 kernel)
-                        if (!HL && m == 0 && nn == 0)
-                            asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[m][nn]) : "v"(az[m]), "v"(bz[nn]));
-                        else
-                            asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[m][nn]) : "v"(az[m]), "v"(bz[nn]));
-                    }
-#endif
-            }
-            asm volatile("" ::: "memory");                       // the refill stays behind the MFMAs that read the registers
-            gather(s, tiN, wN[s]);
-        }
-        if (!hasN) break;
-        // next slot becomes current; its successor's list has arrived; fetch one more
-        tiC = tiN; gC = gN;
-        nkC = (pairs_of(tiC, gC) + 3) >> 2;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) wC[s] = wN[s];
-        hasN = hasNN; tiN = tiNN; gN = gNN;
-        // (hand-issued list loads: one slot old, the 4 k-steps' refills are younger)
-        if constexpr (HL) {   // (the loaded registers are inputs of the statement that waits for them, see above)
-            int li, lo;
-            asm volatile("s_waitcnt vmcnt(%4)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(li), "=&v"(lo) : "v"(rawi), "v"(rawo),
-                         "n"(4 * (MI + NJ)) : "memory");
-            words(li, lo, wN);
-        } else words(rawi, rawo, wN);
-        if (!hasN) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) wN[s] = 0x80000000u;
-        }
-        hasNN = hasN && advance(tiNN, gNN);
-        if (HL) load_list_hl(hasNN ? tiNN : tiN, hasNN ? gNN : gN, rawi, rawo);
-        else load_list(hasNN ? tiNN : tiN, hasNN ? gNN : gN, rawi, rawo);
-    }
-    // hand-issued loads: the last refills are still in flight and hipcc is about to reuse their registers
-    if constexpr (HL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_nop 15" ::: "memory");          // MFMA result -> VALU / memory read: >= 12 wait states
-#pragma unroll
-    for (int m = 0; m < MI; ++m)
-#pragma unroll
-        for (int nn = 0; nn < NJ; ++nn)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ci = ci0 + 16 * m + 4 * q + r, co = co0 + 16 * nn + i;
-                if (ci < a.cin && co < a.cout) {
-                    const float v = acc[m][nn][r] * a.out_scale;          // (1 / loss scale)
+                    float v = acc[m][nn][r];
+                    if constexpr (H) v *= a.out_scale;          // (1 / loss scale)
                     if (v != 0.f) atomicAdd(&a.dw[(int64_t)k * a.dw_kstride + (int64_t)ci * a.lddw + co], v);
                 }
             }
@@ -2161,21 +2006,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_trh_kernel(WgradArgs a) {
     if (live == 0) return;
     unsigned char* const lds = lds_all + wave * 2 * BUF;
 
-    auto pairs_of = [&](int ti, int g) { const int n = __builtin_amdgcn_readlane(cnt, ti) - 16 * g; return n > 16 ? 16 : n; };
-    auto advance = [&](int& ti, int& g) {
-        if (16 * (g + 1) < __builtin_amdgcn_readlane(cnt, ti)) { ++g; return true; }
-        const uint64_t rest_mask = ti >= 63 ? 0ull : (live >> (ti + 1));
-        if (rest_mask == 0) return false;
-        ti = ti + 1 + __builtin_ctzll(rest_mask); g = 0;
-        return true;
-    };
+    const WgradWalk walk{cnt, live};
     const int64_t kbase = (int64_t)k * ldr + t0 * B2M_TILE;
     // entry i of the slot: input row | row inside the tile << 24, bit 31 = no pair
     auto load_word = [&](int ti, int g) -> uint32_t {
         const int64_t base = kbase + (int64_t)ti * B2M_TILE + 16 * g + i;
         const int r_in = a.rb_in[base];
         const uint32_t r_out = a.rb_out[base];
-        return (r_in < 0 || i >= pairs_of(ti, g)) ? 0x80000000u : ((uint32_t)r_in | (r_out << 24));
+        return (r_in < 0 || i >= walk.pairs_of(ti, g)) ? 0x80000000u : ((uint32_t)r_in | (r_out << 24));
     };
     // chunk e = lane + 64 j of an image: pair e / CP, 16-byte chunk e % CP of its row
     int px[NX], py[NY];
@@ -2251,9 +2089,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_trh_kernel(WgradArgs a) {
     // prologue: slot C staged in buffer 0, slot N's rows in flight, slot NN's list entry in flight
     int tiC = __builtin_ctzll(live), gC = 0;
     int tiN = tiC, gN = gC;
-    bool hasN = advance(tiN, gN);
+    bool hasN = walk.advance(tiN, gN);
     int tiNN = tiN, gNN = gN;
-    bool hasNN = hasN && advance(tiNN, gNN);
+    bool hasNN = hasN && walk.advance(tiNN, gNN);
     {
         const uint32_t wC = load_word(tiC, gC);
         const uint32_t wN = hasN ? load_word(tiN, gN) : 0x80000000u;
@@ -2271,7 +2109,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_trh_kernel(WgradArgs a) {
         hasN = hasNN; tiN = tiNN; gN = gNN;
         if (hasN) {
             gather(tiN, wNN);
-            hasNN = advance(tiNN, gNN);
+            hasNN = walk.advance(tiNN, gNN);
             if (hasNN) wNN = load_word(tiNN, gNN);
         }
     }
@@ -2374,8 +2212,8 @@ static void launch_wgrad_block(dim3 grid, hipStream_t st, const WgradArgs& a) {
         return;
     }
     if (a.pipe && a.half) {          // half operands: the flat-pipeline kernel with hipcc-tracked loads, both row-role forms
-        if (a.swap) conv_wgrad_flow_h_kernel<MI, NJ, 1><<<grid, 256, 0, st>>>(a);
-        else conv_wgrad_flow_h_kernel<MI, NJ, 0><<<grid, 256, 0, st>>>(a);
+        if (a.swap) conv_wgrad_flow_kernel<MI, NJ, 2, 1><<<grid, 256, 0, st>>>(a);
+        else conv_wgrad_flow_kernel<MI, NJ, 2, 0><<<grid, 256, 0, st>>>(a);
         return;
     }
     if (a.pipe) {

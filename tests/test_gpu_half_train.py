@@ -51,8 +51,8 @@ CASES = [('k3', 0, (96, 0), 96), ('k3', 0, (96, 32), 96), ('k3', 0, (32, 0), 32)
 
 
 # the three forms of b2m_conv_wgrad_h: f16 MFMA through the transposing LDS read (conv_wgrad_trh_kernel, the default wherever a block
-# is complete and its rows are 16-byte aligned), operands converted on load + fp32 MFMA in the flat pipeline (conv_wgrad_flow_h_kernel),
-# the plain kernel
+# is complete and its rows are 16-byte aligned), operands converted on load + fp32 MFMA in the flat pipeline
+# (conv_wgrad_flow_kernel<.., LOADS = 2>), the plain kernel
 WGRAD_FORMS = {'f16_mfma': {}, 'converted': {'B2M_WGRAD_TRH': '0'}, 'converted_plain': {'B2M_WGRAD_TRH': '0', 'B2M_WGRAD_PIPE': '0'}}
 
 

@@ -202,7 +202,7 @@ def test_the_register_trace_follows_the_path_that_skips_a_wait():
 def test_no_mfma_reads_an_operand_a_valu_instruction_has_just_written(kernels):
     """The flow kernels' MFMAs are asm statements: hipcc pads no hazard for them.  A VGPR written by a VALU instruction (the
     select that zeroes a missing pair's dy, the half form's conversions) is read OLD by an MFMA issued fewer than two wait
-    states later.  Round 6: conv_wgrad_flow_h_kernel<2, 2> -- `v_cndmask v29; v_cndmask v28; v_mfma .., v26, v29` -- added the
+    states later.  Round 6: conv_wgrad_flow_h_kernel<2, 2> (now conv_wgrad_flow_kernel<2, 2, 2>) -- `v_cndmask v29; v_cndmask v28; v_mfma .., v26, v29` -- added the
     UNMASKED dy of missing pairs into the first sub-tile of every block (dW 4 - 40 % too large at the offsets with few pairs),
     while the 3 x 2 block, one conversion further from its first MFMA, was exact; the fp32 form was one `s_waitcnt` away from
     the same.  The cure is `s_nop 1` in the first MFMA statement of a k-step; this is the check on EVERY kernel with MFMAs."""
@@ -237,6 +237,35 @@ def test_the_operand_check_sees_the_hazard_it_is_there_for():
     # a wide accumulator written by a VALU move and read as A two instructions later: still too close by one state
     assert isa_check.mfma_operand_violations(['v_mov_b32_e32 v4, 0', 's_waitcnt vmcnt(3)', 'v_mfma_f32_16x16x4_f32 v[0:3], v4, v5, v[0:3]']) != []
     assert isa_check.mfma_operand_violations(['v_mov_b32_e32 v4, 0', 's_nop 0', 's_waitcnt vmcnt(3)', 'v_mfma_f32_16x16x4_f32 v[0:3], v4, v5, v[0:3]']) == []
+
+
+def test_same_bodies_ignores_label_numbers_and_sees_an_instruction(tmp_path):
+    """isa_check.same_bodies, the comparison a refactor of the kernels is held to: the numbers hipcc gives its labels move with
+    the order of instantiation and do not count, a renamed kernel is found under its new name, one changed instruction counts."""
+    import isa_check
+    asm = """_Z1%sv:
+.LBB%d_1:                                ; =>This Inner Loop Header: Depth=1
+	v_mfma_f32_16x16x4_f32 v[0:3], v4, v5, v[0:3]
+	%s
+	s_cbranch_scc1 .LBB%d_1
+.Ltmp%d:
+	s_endpgm
+	.amdhsa_kernel _Z1%sv
+	.end_amdhsa_kernel
+.Lfunc_end%d:
+; NumVgprs: %d
+"""
+    def write(name, *fill):
+        (tmp_path / name).write_text(asm % fill)
+        return str(tmp_path / name)
+    a = write('a.s', 'a', 7, 's_waitcnt vmcnt(3)', 7, 12, 'a', 7, 6)
+    b = write('b.s', 'b', 104, 's_waitcnt vmcnt(3)', 104, 3, 'b', 104, 6)
+    assert isa_check.same_bodies(a, b, {'_Z1av': '_Z1bv'}) == ([], [], [])
+    assert isa_check.same_bodies(a, b) == (['_Z1av', '_Z1bv'], [], [])
+    c = write('c.s', 'b', 104, 's_waitcnt vmcnt(2)', 104, 3, 'b', 104, 6)
+    assert isa_check.same_bodies(a, c, {'_Z1av': '_Z1bv'}) == ([], ['_Z1bv'], [])
+    d = write('d.s', 'b', 104, 's_waitcnt vmcnt(3)', 104, 3, 'b', 104, 8)
+    assert isa_check.same_bodies(a, d, {'_Z1av': '_Z1bv'}) == ([], [], ['_Z1bv'])
 
 
 def test_half_weight_gradient_reads_its_operands_transposed(kernels):

@@ -73,10 +73,39 @@ def _summarise(body):
     return {'mfma': len(idx), 'loop_waits': waits}
 
 
-def kernel_body(asm_path, name):
-    s = open(asm_path).read()
+def kernel_body(asm_path, name, text=None):
+    s = open(asm_path).read() if text is None else text
     i = s.index(name + ':')
     return s[i:s.index('.end_amdhsa_kernel', i)].split('\n')
+
+
+_NUMBERED = re.compile(r'(\.LBB|\.Ltmp|\.Lfunc_end|\bBB)\d+')
+
+
+def same_bodies(asm_a, asm_b, rename=None):
+    """Are the kernels of two assembly files the same code?  For a refactor that must leave the device code alone (profiles/
+    *_refactor.md): `python tools/isa_check.py A.s B.s [--rename REGEX=REPLACEMENT]`.  `rename` maps kernel names of A to their
+    names in B and is applied inside the bodies as well.  Compared as text, after removing what moves with the order of
+    instantiation alone: the numbers hipcc gives its local labels (`.LBB<n>_`, `.Ltmp<n>`, `.Lfunc_end<n>`, and `BB<n>_` where a loop
+    comment repeats them) and, since the comment column moves with a number's width, runs of blanks.  Returns three sorted lists of
+    names (B's): kernels found in one file only, kernels whose bodies differ, kernels whose kernels() summaries differ."""
+    rename = rename or {}
+    renamed = re.compile('|'.join(sorted(map(re.escape, rename), key=len, reverse=True))) if rename else None
+
+    def bodies(path, old_names):
+        text = open(path).read()
+        out = {}
+        for name, summary in kernels(path).items():
+            body = '\n'.join(kernel_body(path, name, text))
+            if old_names and renamed:
+                body = renamed.sub(lambda m: rename[m.group(0)], body)
+            body = re.sub(r'[ \t]+', ' ', _NUMBERED.sub(r'\1', body))
+            out[rename.get(name, name) if old_names else name] = (body, summary)
+        return out
+
+    a, b = bodies(asm_a, True), bodies(asm_b, False)
+    both = sorted(set(a) & set(b))
+    return (sorted(set(a) ^ set(b)), [n for n in both if a[n][0] != b[n][0]], [n for n in both if a[n][1] != b[n][1]])
 
 
 _REG = re.compile(r'\bv(\d+)\b|\bv\[(\d+):(\d+)\]')
@@ -208,7 +237,24 @@ def mfma_operand_violations(body, states=2):
     return bad
 
 
+def _compare_main(argv):
+    files = [x for x in argv if x.endswith('.s')]
+    rename = {}
+    for spec in (argv[k + 1] for k, x in enumerate(argv[:-1]) if x == '--rename'):
+        pat, repl = spec.split('=', 1)
+        rename.update((n, re.sub(pat, repl, n)) for n in kernels(files[0]) if re.search(pat, n))
+    only, bodies, summaries = same_bodies(files[0], files[1], rename)
+    print('%d / %d kernels, %d renamed; in one file only: %d, bodies that differ: %d, summaries that differ: %d' % (
+        len(kernels(files[0])), len(kernels(files[1])), len(rename), len(only), len(bodies), len(summaries)))
+    for title, names in (('one file only', only), ('body differs', bodies), ('summary differs', summaries)):
+        for n in names:
+            print('  %s: %s' % (title, n))
+    return 1 if only or bodies or summaries else 0
+
+
 if __name__ == '__main__':
+    if len([x for x in sys.argv[1:] if x.endswith('.s')]) == 2:
+        sys.exit(_compare_main(sys.argv[1:]))
     ks = kernels(device_asm())
     pats = sys.argv[1:] or ['conv_fwd_flow_kernel', 'conv_wgrad_flow_kernel', 'conv_stem_kernel', 'conv_1x1']
     for n in sorted(ks):
