@@ -733,8 +733,30 @@ extern "C" int64_t b2m_weight_pack_size(int32_t K, int32_t cin, int32_t cout) {
     return (int64_t)K * nstrip * nchunk * (64 * TW * (KC / 4));
 }
 
-// logical B[k][ci][co]:  transpose == 0:  w[k][ci][co]          (CI = rows, CO = cols)
-//                        transpose == 1:  w[src(k)][sb + co][ci] (CI = cols, CO = sc), src(k) = mirror ? K-1-k : k
+// One packed image: logical B[k][ci][co]:  transpose == 0:  w[k][ci][co]          (CI = rows, CO = cols)
+//                                          transpose == 1:  w[src(k)][sb + co][ci] (CI = cols, CO = sc), src(k) = mirror ? K-1-k : k
+// A plan is a table of these: all layers of a network in one launch, built on the host once, kept on the device.
+struct PackDesc {
+    const float* w; float* wp;
+    int64_t ldw, first_block, total;
+    int32_t K, rows, cols, transpose, mirror, sb, CI, CO, KC, TW;
+};
+// the descriptor of b2m_weight_pack's arguments (first_block 0); false: the channel slice of a transposed image is not inside cin
+static bool pack_desc(PackDesc& e, const float* w, int64_t ldw, int K, int cin, int cout, int transpose, int mirror, int slice_begin,
+                      int slice_count, float* wp) {
+    e = PackDesc{};
+    e.w = w; e.wp = wp; e.ldw = ldw; e.K = K; e.rows = cin; e.cols = cout; e.transpose = transpose; e.mirror = mirror; e.sb = slice_begin;
+    if (!transpose) { e.CI = cin; e.CO = cout; }
+    else {
+        if (!(slice_begin >= 0 && slice_count > 0 && slice_begin + slice_count <= cin)) return false;
+        e.CI = cout; e.CO = slice_count;
+    }
+    e.KC = conv_kc(e.CI); e.TW = conv_tw(e.CO, K);
+    e.total = b2m_weight_pack_size(K, e.CI, e.CO);
+    return true;
+}
+// one image, an element per thread.  It stays beside the plan kernel below, which reads whole row segments through LDS: a second
+// kernel that calls pack_one_block changes the code hipcc makes of weight_pack_batch_kernel (profiles/single_entry_fold.md)
 __global__ void weight_pack_kernel(const float* __restrict__ w, int64_t ldw, int K, int rows, int cols, int transpose,
                                    int mirror, int sb, int CI, int CO, int KC, int TW, float* __restrict__ wp) {
     const int KS = KC / 4, LW = 64 * TW * KS, SW = 16 * TW;
@@ -758,29 +780,16 @@ __global__ void weight_pack_kernel(const float* __restrict__ w, int64_t ldw, int
 }
 extern "C" int b2m_weight_pack(const float* w, int64_t ldw, int32_t K, int32_t cin, int32_t cout, int32_t transpose,
                                int32_t mirror, int32_t slice_begin, int32_t slice_count, float* wp, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     B2M_CHECK_ARG(w && wp && K >= 1 && cin > 0 && cout > 0 && ldw >= cout, "bad arguments");
-    int CI, CO;
-    if (!transpose) { CI = cin; CO = cout; }
-    else {
-        B2M_CHECK_ARG(slice_begin >= 0 && slice_count > 0 && slice_begin + slice_count <= cin, "bad channel slice");
-        CI = cout; CO = slice_count;
-    }
-    const int64_t total = b2m_weight_pack_size(K, CI, CO);
-    int64_t grid = (total + 255) / 256;
+    PackDesc d;
+    B2M_CHECK_ARG(pack_desc(d, w, ldw, K, cin, cout, transpose, mirror, slice_begin, slice_count, wp), "bad channel slice");
+    int64_t grid = (d.total + 255) / 256;
     if (grid > 65536) grid = 65536;
-    weight_pack_kernel<<<(unsigned)grid, 256, 0, st>>>(w, ldw, K, cin, cout, transpose, mirror, slice_begin, CI, CO,
-                                                       conv_kc(CI), conv_tw(CO, K), wp);
+    weight_pack_kernel<<<(unsigned)grid, 256, 0, (hipStream_t)stream>>>(w, ldw, K, cin, cout, transpose, mirror, slice_begin, d.CI, d.CO,
+                                                                       d.KC, d.TW, wp);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }
-
-// ---- all layers of a network in one launch: a plan of descriptors (built on the host once, kept on the device)
-struct PackDesc {
-    const float* w; float* wp;
-    int64_t ldw, first_block, total;
-    int32_t K, rows, cols, transpose, mirror, sb, CI, CO, KC, TW;
-};
 extern "C" int32_t b2m_weight_pack_plan_size(void) { return (int32_t)sizeof(PackDesc); }
 extern "C" int64_t b2m_weight_pack_plan(int32_t n, const int64_t* w, const int64_t* wp, const int64_t* ldw,
                                         const int32_t* K, const int32_t* cin, const int32_t* cout,
@@ -792,19 +801,10 @@ extern "C" int64_t b2m_weight_pack_plan(int32_t n, const int64_t* w, const int64
     int64_t blocks = 0;
     for (int i = 0; i < n; ++i) {
         B2M_CHECK_ARG(w[i] && wp[i] && K[i] >= 1 && cin[i] > 0 && cout[i] > 0 && ldw[i] >= cout[i], "bad layer");
-        PackDesc e;
-        e.w = (const float*)(uintptr_t)w[i]; e.wp = (float*)(uintptr_t)wp[i]; e.ldw = ldw[i];
-        e.K = K[i]; e.rows = cin[i]; e.cols = cout[i]; e.transpose = transpose[i]; e.mirror = mirror[i]; e.sb = slice_begin[i];
-        if (!transpose[i]) { e.CI = cin[i]; e.CO = cout[i]; }
-        else {
-            B2M_CHECK_ARG(slice_begin[i] >= 0 && slice_count[i] > 0 && slice_begin[i] + slice_count[i] <= cin[i], "bad channel slice");
-            e.CI = cout[i]; e.CO = slice_count[i];
-        }
-        e.KC = conv_kc(e.CI); e.TW = conv_tw(e.CO, e.K);
-        e.total = b2m_weight_pack_size(e.K, e.CI, e.CO);
-        e.first_block = blocks;
-        blocks += e.total / (64 * e.TW * (e.KC / 4));          // one workgroup per packed block
-        d[i] = e;
+        B2M_CHECK_ARG(pack_desc(d[i], (const float*)(uintptr_t)w[i], ldw[i], K[i], cin[i], cout[i], transpose[i], mirror[i],
+                                slice_begin[i], slice_count[i], (float*)(uintptr_t)wp[i]), "bad channel slice");
+        d[i].first_block = blocks;
+        blocks += d[i].total / (64 * d[i].TW * (d[i].KC / 4));  // packed blocks: a workgroup takes PACK_PER_WG of them
     }
     return blocks;
 }
@@ -1257,85 +1257,31 @@ extern "C" int64_t b2m_weight_pack_h_size(int32_t K, int32_t c1, int32_t c2, int
     const int TW = conv_tw_h(cout, K);
     return (int64_t)K * ((cout + 16 * TW - 1) / (16 * TW)) * ((c1 + c2) / conv_h_ck(c1, c2)) * (64 * TW * (conv_h_ck(c1, c2) / 4));
 }
-// (source element of logical weight (k, ci, co): w[kk * sk + ci * sci + co * sco], kk = mirror ? K - 1 - k : k -- the plain image
-// has sk = cin * ldw, sci = ldw, sco = 1; the image of the TRANSPOSED weights, the data gradient's operand, exchanges sci and sco)
-__global__ void weight_pack_h_kernel(const float* __restrict__ w, int64_t sk, int64_t sci, int64_t sco, int mirror, int K, int cin,
-                                     int cout, int CK, int TW, _Float16* __restrict__ wp, int64_t total) {
-    const int E = CK / 4, SW = 16 * TW, BLK = 64 * TW * E;
-    const int nchunk = cin / CK, nstrip = (cout + SW - 1) / SW;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int pos = (int)(e % BLK);
-        const int t = pos / (64 * E), lane = (pos / E) % 64, j = pos % E;
-        const int64_t blk = e / BLK;
-        const int chunk = (int)(blk % nchunk); const int64_t b2 = blk / nchunk;
-        const int strip = (int)(b2 % nstrip), k = (int)(b2 / nstrip);
-        const int ci = chunk * CK + E * (lane >> 4) + j, co = strip * SW + 16 * t + (lane & 15);
-        const int kk = mirror ? K - 1 - k : k;
-        wp[e] = (co < cout) ? (_Float16)w[(int64_t)kk * sk + (int64_t)ci * sci + (int64_t)co * sco] : (_Float16)0.f;
-    }
-}
-extern "C" int b2m_weight_pack_h(const float* w, int64_t ldw, int32_t K, int32_t c1, int32_t c2, int32_t cout, void* wp, void* stream) {
-    B2M_CHECK_ARG(w && wp && K >= 1 && c1 > 0 && c2 >= 0 && cout > 0 && ldw >= cout, "bad arguments");
-    B2M_CHECK_ARG(c1 % 16 == 0 && c2 % 16 == 0, "input channels of both sources must be multiples of 16");
-    const int64_t total = b2m_weight_pack_h_size(K, c1, c2, cout);
-    int64_t grid = (total + 255) / 256;
-    if (grid > 65536) grid = 65536;
-    weight_pack_h_kernel<<<(unsigned)grid, 256, 0, (hipStream_t)stream>>>(w, (int64_t)(c1 + c2) * ldw, ldw, 1, 0, K, c1 + c2, cout,
-                                                                         conv_h_ck(c1, c2), conv_tw_h(cout, K), (_Float16*)wp, total);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-// Half image of the TRANSPOSED weights for the data gradient through b2m_conv_fwd_h (half-precision training): the layer's fp32
-// weights W (K, cin, cout, contiguous) -> the image of W'[k] = W[mirror ? K-1-k : k][s0 : s0 + sc, :]^T, i.e. of a layer with
-// cout input channels and sc output channels (b2m_weight_pack_h_size(K, cout, 0, sc) halfs).
-extern "C" int b2m_weight_pack_h_t(const float* w, int32_t K, int32_t cin, int32_t cout, int32_t mirror, int32_t s0, int32_t sc,
-                                   void* wp, void* stream) {
-    B2M_CHECK_ARG(w && wp && K >= 1 && cin > 0 && cout > 0 && s0 >= 0 && sc > 0 && s0 + sc <= cin, "bad arguments");
-    B2M_CHECK_ARG(cout % 16 == 0, "the layer's output channels (the data gradient's input channels) must be a multiple of 16");
-    const int64_t total = b2m_weight_pack_h_size(K, cout, 0, sc);
-    int64_t grid = (total + 255) / 256;
-    if (grid > 65536) grid = 65536;
-    weight_pack_h_kernel<<<(unsigned)grid, 256, 0, (hipStream_t)stream>>>(w + (int64_t)s0 * cout, (int64_t)cin * cout, 1, cout, mirror ? 1 : 0,
-                                                                         K, cout, sc, conv_h_ck(cout, 0), conv_tw_h(sc, K), (_Float16*)wp, total);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-// ---- every half image of a training step in ONE launch (half-precision training: a forward image and one or two transposed
-// images per layer, ~90 per step): a table of descriptors built on the host once (b2m_weight_pack_h_plan), kept on the device.
+// One half image.  Source element of logical weight (k, ci, co): w[kk * sk + ci * sci + co * sco], kk = mirror ? K - 1 - k : k -- the
+// plain image has sk = cin * ldw, sci = ldw, sco = 1; the image of the TRANSPOSED weights, the data gradient's operand, exchanges sci
+// and sco.  A plan is a table of these (half-precision training: a forward image and one or two transposed images per layer, ~90 per
+// step, in ONE launch; built on the host once, kept on the device); the one-image entries hand theirs to the kernel by value.
 struct PackHDesc {
     const float* w; _Float16* wp;
     int64_t sk, sci, sco, total, first_block;
     int32_t mirror, K, cin, cout, CK, TW;
 };
 #define PACKH_PER_WG 2048          // elements of an image per workgroup
-extern "C" int32_t b2m_weight_pack_h_plan_size(void) { return (int32_t)sizeof(PackHDesc); }
-extern "C" int64_t b2m_weight_pack_h_plan(int32_t n, const int64_t* w, const int64_t* wp, const int32_t* K, const int32_t* cin,
-                                          const int32_t* cout, const int32_t* c1, const int32_t* transposed, const int32_t* mirror,
-                                          const int32_t* s0, const int32_t* sc, void* plan_host) {
-    B2M_CHECK_ARG(n >= 0 && (n == 0 || (w && wp && K && cin && cout && c1 && transposed && mirror && s0 && sc && plan_host)), "bad arguments");
-    PackHDesc* d = (PackHDesc*)plan_host;
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        B2M_CHECK_ARG(w[i] && wp[i] && K[i] >= 1 && cin[i] > 0 && cout[i] > 0, "bad layer");
-        PackHDesc e;
-        e.wp = (_Float16*)(uintptr_t)wp[i]; e.K = K[i]; e.sk = (int64_t)cin[i] * cout[i];
-        if (!transposed[i]) {          // b2m_weight_pack_h(w, cout, K, c1, cin - c1, cout)
-            const int c2 = cin[i] - c1[i];
-            B2M_CHECK_ARG(c1[i] > 0 && c2 >= 0 && c1[i] % 16 == 0 && c2 % 16 == 0, "input channels of both sources must be multiples of 16");
-            e.w = (const float*)(uintptr_t)w[i]; e.sci = cout[i]; e.sco = 1; e.mirror = 0;
-            e.cin = cin[i]; e.cout = cout[i]; e.CK = conv_h_ck(c1[i], c2); e.TW = conv_tw_h(cout[i], K[i]);
-            e.total = b2m_weight_pack_h_size(K[i], c1[i], c2, cout[i]);
-        } else {                       // b2m_weight_pack_h_t(w, K, cin, cout, mirror, s0, sc)
-            B2M_CHECK_ARG(s0[i] >= 0 && sc[i] > 0 && s0[i] + sc[i] <= cin[i] && cout[i] % 16 == 0, "bad channel slice");
-            e.w = (const float*)(uintptr_t)w[i] + (int64_t)s0[i] * cout[i]; e.sci = 1; e.sco = cout[i]; e.mirror = mirror[i] ? 1 : 0;
-            e.cin = cout[i]; e.cout = sc[i]; e.CK = conv_h_ck(cout[i], 0); e.TW = conv_tw_h(sc[i], K[i]);
-            e.total = b2m_weight_pack_h_size(K[i], cout[i], 0, sc[i]);
-        }
-        e.first_block = blocks;
-        blocks += cdiv64(e.total, PACKH_PER_WG);
-        d[i] = e;
-    }
-    return blocks;
+// element e of image d
+__device__ __forceinline__ void pack_h_element(const PackHDesc& d, int64_t e) {
+    const int E = d.CK / 4, SW = 16 * d.TW, BLK = 64 * d.TW * E;
+    const int nchunk = d.cin / d.CK, nstrip = (d.cout + SW - 1) / SW;
+    const int pos = (int)(e % BLK);
+    const int t = pos / (64 * E), lane = (pos / E) % 64, j = pos % E;
+    const int64_t blk = e / BLK;
+    const int chunk = (int)(blk % nchunk); const int64_t b2 = blk / nchunk;
+    const int strip = (int)(b2 % nstrip), k = (int)(b2 / nstrip);
+    const int ci = chunk * d.CK + E * (lane >> 4) + j, co = strip * SW + 16 * t + (lane & 15);
+    const int kk = d.mirror ? d.K - 1 - k : k;
+    d.wp[e] = (co < d.cout) ? (_Float16)d.w[(int64_t)kk * d.sk + (int64_t)ci * d.sci + (int64_t)co * d.sco] : (_Float16)0.f;
+}
+__global__ void weight_pack_h_kernel(PackHDesc d) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < d.total; e += (int64_t)gridDim.x * blockDim.x) pack_h_element(d, e);
 }
 __global__ __launch_bounds__(256) void weight_pack_h_batch_kernel(const PackHDesc* __restrict__ plan, int n) {
     // the image of this workgroup: the last descriptor whose first block is not behind it
@@ -1345,21 +1291,69 @@ __global__ __launch_bounds__(256) void weight_pack_h_batch_kernel(const PackHDes
         if (plan[mid].first_block <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
     }
     const PackHDesc d = plan[lo];
-    const int E = d.CK / 4, SW = 16 * d.TW, BLK = 64 * d.TW * E;
-    const int nchunk = d.cin / d.CK, nstrip = (d.cout + SW - 1) / SW;
     const int64_t e0 = ((int64_t)blockIdx.x - d.first_block) * PACKH_PER_WG;
     for (int u = threadIdx.x; u < PACKH_PER_WG; u += 256) {
-        const int64_t e = e0 + u;
-        if (e >= d.total) break;
-        const int pos = (int)(e % BLK);
-        const int t = pos / (64 * E), lane = (pos / E) % 64, j = pos % E;
-        const int64_t blk = e / BLK;
-        const int chunk = (int)(blk % nchunk); const int64_t b2 = blk / nchunk;
-        const int strip = (int)(b2 % nstrip), k = (int)(b2 / nstrip);
-        const int ci = chunk * d.CK + E * (lane >> 4) + j, co = strip * SW + 16 * t + (lane & 15);
-        const int kk = d.mirror ? d.K - 1 - k : k;
-        d.wp[e] = (co < d.cout) ? (_Float16)d.w[(int64_t)kk * d.sk + (int64_t)ci * d.sci + (int64_t)co * d.sco] : (_Float16)0.f;
+        if (e0 + u >= d.total) break;
+        pack_h_element(d, e0 + u);
     }
+}
+// The descriptor (first_block 0) of the image of the fp32 weights w, (K, cin) rows of pitch ldw with cout columns.  Plain: the layer's
+// own image, c1 of the cin input channels from the first source.  Transposed: the image of W'[k] = W[mirror ? K-1-k : k][s0 : s0 + sc, :]^T,
+// a layer with cout input channels and sc output channels.  (The callers have checked the channel counts.)
+static PackHDesc pack_h_desc(const float* w, int64_t ldw, int K, int cin, int cout, int c1, int transposed, int mirror, int s0, int sc,
+                             void* wp) {
+    PackHDesc e{};
+    e.wp = (_Float16*)wp; e.K = K; e.sk = (int64_t)cin * ldw;
+    int c2;
+    if (!transposed) { e.w = w; e.sci = ldw; e.sco = 1; e.cout = cout; c2 = cin - c1; }
+    else { e.w = w + (int64_t)s0 * ldw; e.sci = 1; e.sco = ldw; e.mirror = mirror ? 1 : 0; e.cout = sc; c1 = cout; c2 = 0; }
+    e.cin = c1 + c2; e.CK = conv_h_ck(c1, c2); e.TW = conv_tw_h(e.cout, K);
+    e.total = b2m_weight_pack_h_size(K, c1, c2, e.cout);
+    return e;
+}
+static void pack_h_launch(const PackHDesc& d, void* stream) {
+    int64_t grid = (d.total + 255) / 256;
+    if (grid > 65536) grid = 65536;
+    weight_pack_h_kernel<<<(unsigned)grid, 256, 0, (hipStream_t)stream>>>(d);
+}
+extern "C" int b2m_weight_pack_h(const float* w, int64_t ldw, int32_t K, int32_t c1, int32_t c2, int32_t cout, void* wp, void* stream) {
+    B2M_CHECK_ARG(w && wp && K >= 1 && c1 > 0 && c2 >= 0 && cout > 0 && ldw >= cout, "bad arguments");
+    B2M_CHECK_ARG(c1 % 16 == 0 && c2 % 16 == 0, "input channels of both sources must be multiples of 16");
+    pack_h_launch(pack_h_desc(w, ldw, K, c1 + c2, cout, c1, 0, 0, 0, 0, wp), stream);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+// Half image of the TRANSPOSED weights for the data gradient through b2m_conv_fwd_h (half-precision training): the layer's fp32
+// weights W (K, cin, cout, contiguous) -> the image of a layer with cout input channels and sc output channels
+// (b2m_weight_pack_h_size(K, cout, 0, sc) halfs).
+extern "C" int b2m_weight_pack_h_t(const float* w, int32_t K, int32_t cin, int32_t cout, int32_t mirror, int32_t s0, int32_t sc,
+                                   void* wp, void* stream) {
+    B2M_CHECK_ARG(w && wp && K >= 1 && cin > 0 && cout > 0 && s0 >= 0 && sc > 0 && s0 + sc <= cin, "bad arguments");
+    B2M_CHECK_ARG(cout % 16 == 0, "the layer's output channels (the data gradient's input channels) must be a multiple of 16");
+    pack_h_launch(pack_h_desc(w, cout, K, cin, cout, 0, 1, mirror, s0, sc, wp), stream);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+// ---- every half image of a training step in ONE launch, of contiguous weights
+extern "C" int32_t b2m_weight_pack_h_plan_size(void) { return (int32_t)sizeof(PackHDesc); }
+extern "C" int64_t b2m_weight_pack_h_plan(int32_t n, const int64_t* w, const int64_t* wp, const int32_t* K, const int32_t* cin,
+                                          const int32_t* cout, const int32_t* c1, const int32_t* transposed, const int32_t* mirror,
+                                          const int32_t* s0, const int32_t* sc, void* plan_host) {
+    B2M_CHECK_ARG(n >= 0 && (n == 0 || (w && wp && K && cin && cout && c1 && transposed && mirror && s0 && sc && plan_host)), "bad arguments");
+    PackHDesc* d = (PackHDesc*)plan_host;
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        B2M_CHECK_ARG(w[i] && wp[i] && K[i] >= 1 && cin[i] > 0 && cout[i] > 0, "bad layer");
+        if (!transposed[i])
+            B2M_CHECK_ARG(c1[i] > 0 && cin[i] - c1[i] >= 0 && c1[i] % 16 == 0 && (cin[i] - c1[i]) % 16 == 0,
+                          "input channels of both sources must be multiples of 16");
+        else B2M_CHECK_ARG(s0[i] >= 0 && sc[i] > 0 && s0[i] + sc[i] <= cin[i] && cout[i] % 16 == 0, "bad channel slice");
+        d[i] = pack_h_desc((const float*)(uintptr_t)w[i], cout[i], K[i], cin[i], cout[i], c1[i], transposed[i], mirror[i], s0[i], sc[i],
+                           (void*)(uintptr_t)wp[i]);
+        d[i].first_block = blocks;
+        blocks += cdiv64(d[i].total, PACKH_PER_WG);
+    }
+    return blocks;
 }
 extern "C" int b2m_weight_pack_h_run(const void* plan_dev, int32_t n, int64_t total_blocks, void* stream) {
     B2M_CHECK_ARG(n >= 0 && total_blocks >= 0 && total_blocks < (1ll << 31) && (n == 0 || plan_dev), "bad arguments");

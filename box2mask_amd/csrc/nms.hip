@@ -337,130 +337,6 @@ extern "C" int b2m_nmc(const float* boxes, int32_t n, float cluster_th, int32_t 
     return B2M_OK;
 }
 
-// ------------------------------------------------------------------ heat-maps -> voxel bit masks
-__global__ __launch_bounds__(256) void mask_project_kernel(const float* __restrict__ heat, int n_fg,
-                                                           const int32_t* __restrict__ sel,
-                                                           const int32_t* __restrict__ fg_slot,
-                                                           const int64_t* __restrict__ seg2vox, int64_t n_vox, float th,
-                                                           uint64_t* __restrict__ bits, int64_t words) {
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int r = blockIdx.y;
-    if (w >= words) return;
-    const int64_t v = w * 64 + lane_id();
-    bool bit = false;
-    if (v < n_vox) {
-        const int slot = fg_slot[seg2vox[v]];
-        const float val = slot >= 0 ? heat[(int64_t)sel[r] * n_fg + slot] : 0.f;
-        bit = val > th;
-    }
-    const uint64_t m = __ballot(bit);
-    if (lane_id() == 0) bits[(int64_t)r * words + w] = m;
-}
-extern "C" int b2m_mask_project(const float* heat, int32_t n_fg, const int32_t* sel, int32_t ksel,
-                                const int32_t* fg_slot, const int64_t* seg2vox, int64_t n_vox, float mask_bin_th,
-                                uint64_t* bits, int64_t words, void* stream) {
-    B2M_CHECK_ARG(ksel >= 0 && words == cdiv64(n_vox, 64), "bad sizes");
-    if (ksel == 0 || n_vox == 0) return B2M_OK;        // no cluster passed the score filter: nothing to project
-    B2M_CHECK_ARG(heat && sel && fg_slot && seg2vox && bits && n_fg > 0, "bad arguments");
-    dim3 grid((unsigned)cdiv64(words, 4), (unsigned)ksel);
-    mask_project_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(heat, n_fg, sel, fg_slot, seg2vox, n_vox, mask_bin_th,
-                                                               bits, words);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-
-// ------------------------------------------------------------------ mask NMS
-__global__ __launch_bounds__(256) void mask_inter_kernel(const uint64_t* __restrict__ bits, int k, int64_t words,
-                                                         int32_t* __restrict__ inter) {
-    const int i = blockIdx.y, j = blockIdx.x;
-    if (j < i) return;
-    __shared__ int wsum[4];
-    int s = 0;
-    const uint64_t* a = bits + (int64_t)i * words;
-    const uint64_t* b = bits + (int64_t)j * words;
-    for (int64_t w = threadIdx.x; w < words; w += 256) s += __popcll(a[w] & b[w]);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-    if (lane_id() == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int t = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        inter[(int64_t)i * k + j] = t;
-        inter[(int64_t)j * k + i] = t;
-    }
-}
-__global__ __launch_bounds__(256) void mask_greedy_kernel(const int32_t* __restrict__ inter, int k, float th,
-                                                          int32_t* __restrict__ keep, int32_t* __restrict__ n_keep) {
-    // keep[] doubles as the alive flag: 1 = still remaining / kept, 0 = suppressed
-    for (int j = threadIdx.x; j < k; j += 256) keep[j] = 1;
-    __syncthreads();
-    int nk = 0;
-    for (int i = 0; i < k; ++i) {
-        if (keep[i]) {                                           // uniform: all threads read the same word
-            ++nk;
-            const int ci = inter[(int64_t)i * k + i];
-            for (int j = i + 1 + threadIdx.x; j < k; j += 256) {
-                if (!keep[j]) continue;
-                const int in = inter[(int64_t)i * k + j];
-                const int un = ci + inter[(int64_t)j * k + j] - in;
-                const float iou = (float)in / (float)un;         // int64 true-division -> float32 in torch
-                if (!(iou <= th)) keep[j] = 0;                   // iou_nms.py:138 keeps `ious <= th`
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *n_keep = nk;
-}
-extern "C" int b2m_mask_nms(const uint64_t* bits, int32_t k, int64_t words, float th, int32_t* inter, int32_t* keep,
-                            int32_t* n_keep, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    B2M_CHECK_ARG(bits && inter && keep && n_keep && k >= 0 && k <= 65535 && words >= 0, "bad arguments");
-    if (k == 0) { B2M_HIP(hipMemsetAsync(n_keep, 0, sizeof(int32_t), st)); return B2M_OK; }
-    mask_inter_kernel<<<dim3((unsigned)k, (unsigned)k), 256, 0, st>>>(bits, k, words, inter);
-    mask_greedy_kernel<<<1, 256, 0, st>>>(inter, k, th, keep, n_keep);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-
-// ------------------------------------------------------------------ per-instance label histogram
-__global__ __launch_bounds__(256) void label_hist_kernel(const uint64_t* __restrict__ bits, int64_t words,
-                                                         const int32_t* __restrict__ rows,
-                                                         const int32_t* __restrict__ sem, int64_t n_vox, int n_class,
-                                                         int32_t* __restrict__ labels) {
-    __shared__ int hist[256];
-    const int r = blockIdx.x;
-    const int64_t row = rows ? rows[r] : r;
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    for (int64_t w = threadIdx.x; w < words; w += 256) {
-        uint64_t m = bits[row * words + w];
-        while (m) {
-            const int b = __builtin_ctzll(m);
-            m &= m - 1;
-            const int64_t v = w * 64 + b;
-            if (v < n_vox) {
-                const int c = sem[v];
-                if (c >= 0 && c < n_class) atomicAdd(&hist[c], 1);
-            }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int best = 0, bc = hist[0];
-        for (int c = 1; c < n_class; ++c) if (hist[c] > bc) { bc = hist[c]; best = c; }   // first maximum (np.argmax)
-        labels[r] = best;
-    }
-}
-extern "C" int b2m_label_hist(const uint64_t* bits, int64_t words, const int32_t* rows, int32_t k, const int32_t* sem,
-                              int64_t n_vox, int32_t n_class, int32_t* labels, void* stream) {
-    B2M_CHECK_ARG(k >= 0 && n_class >= 1 && n_class <= 256, "bad sizes (n_class <= 256)");
-    if (k == 0) return B2M_OK;
-    B2M_CHECK_ARG(bits && sem && labels, "NULL argument");
-    label_hist_kernel<<<(unsigned)k, 256, 0, (hipStream_t)stream>>>(bits, words, rows, sem, n_vox, n_class, labels);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-
 // ------------------------------------------------------------------ full label histogram of every mask row
 // hist[r][c] = |{v in mask r : label[v] == c}|: the prediction x ground-truth-instance intersection counts of
 // assign_instances_for_scan (/root/reference/utils/eval_metric.py:316-330), all pairs in one pass over the bits.
@@ -505,27 +381,6 @@ extern "C" int b2m_mask_hist(const uint64_t* bits, int64_t words, int32_t k, con
     return B2M_OK;
 }
 
-// ------------------------------------------------------------------ bit rows -> byte masks through an index
-__global__ void mask_gather_kernel(const uint64_t* __restrict__ bits, int64_t words, const int32_t* __restrict__ rows,
-                                   const int64_t* __restrict__ index, int64_t n_pts, uint8_t* __restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int r = blockIdx.y;
-    if (p >= n_pts) return;
-    const int64_t row = rows ? rows[r] : r;
-    const int64_t v = index ? index[p] : p;
-    out[(int64_t)r * n_pts + p] = (uint8_t)((bits[row * words + (v >> 6)] >> (v & 63)) & 1ull);
-}
-extern "C" int b2m_mask_gather(const uint64_t* bits, int64_t words, const int32_t* rows, int32_t k,
-                               const int64_t* index, int64_t n_pts, uint8_t* out, void* stream) {
-    B2M_CHECK_ARG(k >= 0 && k <= 65535 && n_pts >= 0, "bad sizes");
-    if (k == 0 || n_pts == 0) return B2M_OK;            // empty selection: nothing to write (out may be NULL)
-    B2M_CHECK_ARG(bits && out, "NULL argument");
-    mask_gather_kernel<<<dim3((unsigned)cdiv64(n_pts, 256), (unsigned)k), 256, 0, (hipStream_t)stream>>>(
-        bits, words, rows, index, n_pts, out);
-    B2M_LAUNCH_CHECK();
-    return B2M_OK;
-}
-
 // ------------------------------------------------------------------ bool rows -> bit rows
 __global__ __launch_bounds__(256) void mask_pack_kernel(const uint8_t* __restrict__ masks, int64_t n,
                                                         uint64_t* __restrict__ bits, int64_t words) {
@@ -546,11 +401,15 @@ extern "C" int b2m_mask_pack(const uint8_t* masks, int32_t k, int64_t n, uint64_
     return B2M_OK;
 }
 
-// ------------------------------------------------------------------ the mask stages for ALL scenes of a batch
-// detection2mask walks the scenes of a batch (/root/reference/models/detection_net.py:390-477); per scene the kernels above
-// are a few microseconds of work behind a launch each (8 scenes: 32 launches, label_hist 0.42 ms at 16 GB/s).  Here one
-// launch per stage covers every (scene, instance) row: a table of B2M_MASK_DESC int64 fields per scene (include/b2m.h) holds
-// the scene's pointers and sizes, a block finds its scene from the running row counts in the table.
+// ------------------------------------------------------------------ the mask stages: projection, NMS, labels, gather
+// detection2mask walks the scenes of a batch (/root/reference/models/detection_net.py:390-477); per scene a stage is a few
+// microseconds of work behind a launch (8 scenes: 32 launches).  One launch per stage covers every (scene, instance) row: a
+// table of B2M_MASK_DESC int64 fields per scene (include/b2m.h) holds the scene's pointers and sizes, a block finds its scene
+// from the running row counts in the table.  Projection, the intersection table and the gather are ONE __device__ body each that
+// reads the scene's descriptor at p: *_batch_kernel passes a row of the table, the single-scene kernel of b2m_mask_project /
+// b2m_mask_nms / b2m_mask_nms_sweep / b2m_mask_gather its own argument -- the descriptor by value, filled on the host from the
+// entry's pointers (fields a stage does not read stay zero).  The greedy walk is one function; the label histogram keeps a
+// single-scene kernel of its own.
 struct MaskScene {
     const float* heat; int64_t n_fg; const int32_t* sel; int64_t ksel; const int32_t* fg_slot; const int64_t* seg2vox;
     int64_t n_vox; uint64_t* bits; int64_t words; int32_t* inter; int32_t* keep; const int32_t* rows; int64_t kk;
@@ -565,12 +424,12 @@ __device__ __forceinline__ int scene_of_row(const MaskScene* sc, int n_scenes, i
     }
     return -1;
 }
+// ---- heat-maps -> voxel bit masks
 // Round 5: a wave owns one 64-voxel word of a scene for ALL of the scene's selected rows -- the voxel's segment and foreground slot
 // (seg2vox, fg_slot: 12 bytes per voxel) are read once instead of once per row (PMC: 4.8 x the algorithmic bytes before); lane r
 // collects row r's word and the wave writes up to 64 rows' words with one instruction.
-__global__ __launch_bounds__(256) void mask_project_batch_kernel(const MaskScene* __restrict__ sc, int n_scenes, float th) {
-    if ((int)blockIdx.y >= n_scenes) return;
-    const MaskScene d = sc[blockIdx.y];
+__device__ __forceinline__ void mask_project(const MaskScene* __restrict__ p, float th) {
+    const MaskScene d = *p;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= d.words || d.ksel == 0) return;
     const int lane = lane_id();
@@ -587,9 +446,15 @@ __global__ __launch_bounds__(256) void mask_project_batch_kernel(const MaskScene
         if (lane < nr) d.bits[(r0 + lane) * d.words + w] = mine;
     }
 }
-// (sweep: the table is wanted whatever field 10 says -- b2m_mask_nms_sweep_batch writes its flags elsewhere)
-__global__ __launch_bounds__(256) void mask_inter_batch_kernel(const MaskScene* __restrict__ sc, bool sweep) {
-    const MaskScene d = sc[blockIdx.z];
+__global__ __launch_bounds__(256) void mask_project_batch_kernel(const MaskScene* __restrict__ sc, int n_scenes, float th) {
+    if ((int)blockIdx.y >= n_scenes) return;
+    mask_project(sc + blockIdx.y, th);
+}
+__global__ __launch_bounds__(256) void mask_project_kernel(MaskScene d, float th) { mask_project(&d, th); }
+// ---- mask NMS: intersection table, then the greedy walk
+// (sweep: the table is wanted whatever field 10 says -- the sweeps and the single-scene entries write their flags elsewhere)
+__device__ __forceinline__ void mask_inter(const MaskScene* __restrict__ p, bool sweep) {
+    const MaskScene d = *p;
     const int i = blockIdx.y, j = blockIdx.x, k = (int)d.ksel;
     if (i >= k || j >= k || j < i || (d.keep == nullptr && !sweep)) return;
     __shared__ int wsum[4];
@@ -607,23 +472,31 @@ __global__ __launch_bounds__(256) void mask_inter_batch_kernel(const MaskScene* 
         d.inter[(int64_t)j * k + i] = t;
     }
 }
-// the greedy walk of one workgroup of 256 threads over a k x k intersection table: keep[] doubles as the alive flag
-__device__ __forceinline__ void mask_greedy_walk(const int32_t* __restrict__ inter, int k, float th, int32_t* __restrict__ keep) {
+__global__ __launch_bounds__(256) void mask_inter_batch_kernel(const MaskScene* __restrict__ sc, bool sweep) {
+    mask_inter(sc + blockIdx.z, sweep);
+}
+__global__ __launch_bounds__(256) void mask_inter_kernel(MaskScene d) { mask_inter(&d, true); }
+// the greedy walk of one workgroup of 256 threads over a k x k intersection table: keep[] doubles as the alive flag (1 = still
+// remaining / kept, 0 = suppressed).  Returns the number of kept rows, the same in every thread: all read the same keep[i]
+__device__ __forceinline__ int mask_greedy_walk(const int32_t* __restrict__ inter, int k, float th, int32_t* __restrict__ keep) {
     for (int j = threadIdx.x; j < k; j += 256) keep[j] = 1;
     __syncthreads();
+    int nk = 0;
     for (int i = 0; i < k; ++i) {
         if (keep[i]) {
+            ++nk;
             const int ci = inter[(int64_t)i * k + i];
             for (int j = i + 1 + threadIdx.x; j < k; j += 256) {
                 if (!keep[j]) continue;
                 const int in = inter[(int64_t)i * k + j];
                 const int un = ci + inter[(int64_t)j * k + j] - in;
-                const float iou = (float)in / (float)un;
-                if (!(iou <= th)) keep[j] = 0;
+                const float iou = (float)in / (float)un;         // int64 true-division -> float32 in torch
+                if (!(iou <= th)) keep[j] = 0;                   // iou_nms.py:138 keeps `ious <= th`
             }
         }
         __syncthreads();
     }
+    return nk;
 }
 __global__ __launch_bounds__(256) void mask_greedy_batch_kernel(const MaskScene* __restrict__ sc, float th) {
     const MaskScene d = sc[blockIdx.x];
@@ -631,6 +504,12 @@ __global__ __launch_bounds__(256) void mask_greedy_batch_kernel(const MaskScene*
     if (d.keep == nullptr || k == 0) return;
     mask_greedy_walk(d.inter, k, th, d.keep);
 }
+__global__ __launch_bounds__(256) void mask_greedy_kernel(const int32_t* __restrict__ inter, int k, float th,
+                                                          int32_t* __restrict__ keep, int32_t* __restrict__ n_keep) {
+    const int nk = mask_greedy_walk(inter, k, th, keep);
+    if (threadIdx.x == 0) *n_keep = nk;
+}
+// ---- per-instance label histogram
 // label histogram of a mask row.  A wave reads 64 consecutive words of the bit row at once (512 contiguous bytes) and then
 // works only on the non-zero ones, all 64 lanes on the 64 voxels of one word (a coalesced read of their labels): a thread
 // per word walked its set bits one by one behind a 4-byte gather each (round 2: 0.42 ms per batch at 16 GB/s).
@@ -666,11 +545,42 @@ __global__ __launch_bounds__(256) void label_hist_batch_kernel(const MaskScene* 
         d.labels[r] = best;
     }
 }
-// bit rows -> byte masks of ALL kept rows of a scene: a thread owns four consecutive output points, reads their voxel
-// indices ONCE (the per-row kernel re-read the 8-byte index for every instance: 99 x 9.6 MB on the benchmark batch) and
-// writes one 4-byte word per row
-__global__ __launch_bounds__(256) void mask_gather_batch_kernel(const MaskScene* __restrict__ sc) {
-    const MaskScene d = sc[blockIdx.y];
+// one scene by its pointers: a thread per word walks its set bits.  On ONE scene the wave-per-64-words body above is slower (k rows
+// are k workgroups: 55 -> 127 us on a 150 k-voxel scene, 268 -> 467 us for 4 rows over the 1.2 M points of an S3DIS room;
+// profiles/single_entry_fold.md section 6), so this stage keeps its single-scene kernel
+__global__ __launch_bounds__(256) void label_hist_kernel(const uint64_t* __restrict__ bits, int64_t words,
+                                                         const int32_t* __restrict__ rows,
+                                                         const int32_t* __restrict__ sem, int64_t n_vox, int n_class,
+                                                         int32_t* __restrict__ labels) {
+    __shared__ int hist[256];
+    const int r = blockIdx.x;
+    const int64_t row = rows ? rows[r] : r;
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (int64_t w = threadIdx.x; w < words; w += 256) {
+        uint64_t m = bits[row * words + w];
+        while (m) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1;
+            const int64_t v = w * 64 + b;
+            if (v < n_vox) {
+                const int c = sem[v];
+                if (c >= 0 && c < n_class) atomicAdd(&hist[c], 1);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int best = 0, bc = hist[0];
+        for (int c = 1; c < n_class; ++c) if (hist[c] > bc) { bc = hist[c]; best = c; }   // first maximum (np.argmax)
+        labels[r] = best;
+    }
+}
+// ---- bit rows -> byte masks through an index
+// ALL kept rows of a scene: a thread owns four consecutive output points, reads their voxel indices ONCE (a kernel per row
+// re-read the 8-byte index for every instance: 99 x 9.6 MB on the benchmark batch) and writes one 4-byte word per row
+__device__ __forceinline__ void mask_gather(const MaskScene* __restrict__ p) {
+    const MaskScene d = *p;
     const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (p0 >= d.n_pts || d.kk == 0) return;
     int64_t v[4];
@@ -693,6 +603,63 @@ __global__ __launch_bounds__(256) void mask_gather_batch_kernel(const MaskScene*
         }
     }
 }
+__global__ __launch_bounds__(256) void mask_gather_batch_kernel(const MaskScene* __restrict__ sc) {
+    mask_gather(sc + blockIdx.y);
+}
+__global__ __launch_bounds__(256) void mask_gather_kernel(MaskScene d) { mask_gather(&d); }
+
+// ---- one scene given by its pointers
+extern "C" int b2m_mask_project(const float* heat, int32_t n_fg, const int32_t* sel, int32_t ksel,
+                                const int32_t* fg_slot, const int64_t* seg2vox, int64_t n_vox, float mask_bin_th,
+                                uint64_t* bits, int64_t words, void* stream) {
+    B2M_CHECK_ARG(ksel >= 0 && words == cdiv64(n_vox, 64), "bad sizes");
+    if (ksel == 0 || n_vox == 0) return B2M_OK;        // no cluster passed the score filter: nothing to project
+    B2M_CHECK_ARG(heat && sel && fg_slot && seg2vox && bits && n_fg > 0, "bad arguments");
+    MaskScene d{};
+    d.heat = heat; d.n_fg = n_fg; d.sel = sel; d.ksel = ksel; d.fg_slot = fg_slot; d.seg2vox = seg2vox; d.n_vox = n_vox;
+    d.bits = bits; d.words = words;
+    mask_project_kernel<<<(unsigned)cdiv64(words, 4), 256, 0, (hipStream_t)stream>>>(d, mask_bin_th);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+// the k x k intersection table of one scene's bit rows (b2m_mask_nms, b2m_mask_nms_sweep)
+static void mask_inter_launch(const uint64_t* bits, int32_t k, int64_t words, int32_t* inter, hipStream_t st) {
+    MaskScene d{};
+    d.bits = const_cast<uint64_t*>(bits); d.ksel = k; d.words = words; d.inter = inter;
+    mask_inter_kernel<<<dim3((unsigned)k, (unsigned)k), 256, 0, st>>>(d);
+}
+extern "C" int b2m_mask_nms(const uint64_t* bits, int32_t k, int64_t words, float th, int32_t* inter, int32_t* keep,
+                            int32_t* n_keep, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(bits && inter && keep && n_keep && k >= 0 && k <= 65535 && words >= 0, "bad arguments");
+    if (k == 0) { B2M_HIP(hipMemsetAsync(n_keep, 0, sizeof(int32_t), st)); return B2M_OK; }
+    mask_inter_launch(bits, k, words, inter, st);
+    mask_greedy_kernel<<<1, 256, 0, st>>>(inter, k, th, keep, n_keep);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+extern "C" int b2m_label_hist(const uint64_t* bits, int64_t words, const int32_t* rows, int32_t k, const int32_t* sem,
+                              int64_t n_vox, int32_t n_class, int32_t* labels, void* stream) {
+    B2M_CHECK_ARG(k >= 0 && n_class >= 1 && n_class <= 256, "bad sizes (n_class <= 256)");
+    if (k == 0) return B2M_OK;
+    B2M_CHECK_ARG(bits && sem && labels, "NULL argument");
+    label_hist_kernel<<<(unsigned)k, 256, 0, (hipStream_t)stream>>>(bits, words, rows, sem, n_vox, n_class, labels);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+
+extern "C" int b2m_mask_gather(const uint64_t* bits, int64_t words, const int32_t* rows, int32_t k,
+                               const int64_t* index, int64_t n_pts, uint8_t* out, void* stream) {
+    B2M_CHECK_ARG(k >= 0 && k <= 65535 && n_pts >= 0, "bad sizes");
+    if (k == 0 || n_pts == 0) return B2M_OK;            // empty selection: nothing to write (out may be NULL)
+    B2M_CHECK_ARG(bits && out, "NULL argument");
+    MaskScene d{};
+    d.bits = const_cast<uint64_t*>(bits); d.words = words; d.rows = rows; d.kk = k; d.index = index; d.n_pts = n_pts; d.out = out;
+    mask_gather_kernel<<<(unsigned)cdiv64(n_pts, 1024), 256, 0, (hipStream_t)stream>>>(d);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+// ---- all scenes of a batch: the table
 extern "C" int b2m_mask_project_batch(const int64_t* desc, int32_t n_scenes, int64_t total_sel, int64_t max_words,
                                       float mask_bin_th, void* stream) {
     B2M_CHECK_ARG(n_scenes >= 0 && total_sel >= 0 && total_sel <= 65535 && max_words >= 0, "bad sizes (at most 65535 rows per batch)");
@@ -845,7 +812,7 @@ extern "C" int b2m_mask_nms_sweep(const uint64_t* bits, int32_t k, int64_t words
     B2M_CHECK_ARG(k >= 0 && k <= 65535 && words >= 0, "bad sizes");
     if (k == 0) return B2M_OK;
     B2M_CHECK_ARG(bits && inter && keep, "NULL argument");
-    mask_inter_kernel<<<dim3((unsigned)k, (unsigned)k), 256, 0, st>>>(bits, k, words, inter);
+    mask_inter_launch(bits, k, words, inter, st);
     mask_greedy_sweep_kernel<<<(unsigned)n_th, 256, 0, st>>>(inter, k, t, keep);
     B2M_LAUNCH_CHECK();
     return B2M_OK;

@@ -559,7 +559,8 @@ int b2m_nmc_batch(const float* boxes, const int64_t* desc, int32_t n_scenes, int
 /* Heat-map rows -> voxel bit masks.  For selected cluster rows sel[0:ksel] of heat (k x n_fg):
  * value(v) = fg_slot[seg2vox[v]] >= 0 ? heat[sel[r], fg_slot[seg2vox[v]]] : 0;
  * bit v of bits[r*words + v/64] = value(v) > mask_bin_th.  Replaces models/detection_net.py:436-446
- * (zero-padded background, projection through seg2vox, threshold).  words = ceil(n_vox/64). */
+ * (zero-padded background, projection through seg2vox, threshold).  words = ceil(n_vox/64).
+ * A single scene runs the body of b2m_mask_project_batch, its descriptor by value. */
 int b2m_mask_project(const float* heat, int32_t n_fg, const int32_t* sel, int32_t ksel,
                      const int32_t* fg_slot, const int64_t* seg2vox, int64_t n_vox, float mask_bin_th,
                      uint64_t* bits, int64_t words, void* stream);
@@ -567,13 +568,15 @@ int b2m_mask_project(const float* heat, int32_t n_fg, const int32_t* sel, int32_
 /* Greedy mask NMS in the given (score-descending) order; IoU = |a&b| / |a|b| from popcounts,
  * evaluated as float32(inter)/float32(union) like torch's int64 true-division.
  * Replaces mask_NMS(sorted_masks, th), models/iou_nms.py:130-144 (masks_iou 109-121).
- * inter: int32[k*k] scratch, keep[k] int32 flags out, *n_keep device int32. */
+ * inter: int32[k*k] scratch, keep[k] int32 flags out, *n_keep device int32.
+ * A single scene runs the bodies of b2m_mask_nms_batch (intersection table, greedy walk), its descriptor by value. */
 int b2m_mask_nms(const uint64_t* bits, int32_t k, int64_t words, float th,
                  int32_t* inter, int32_t* keep, int32_t* n_keep, void* stream);
 
 /* labels[r] = argmax_c |{v in mask rows[r] : sem[v]==c}| (lowest c on ties; 0 for an empty mask).
  * Replaces the bincount/argmax loop of models/detection_net.py:461-466.  0 <= sem < n_class <= 256.
- * rows: int32[k] mask row per output (NULL = identity). */
+ * rows: int32[k] mask row per output (NULL = identity).  (A kernel of its own: on one scene the body of b2m_label_hist_batch
+ * measured slower, profiles/single_entry_fold.md.) */
 int b2m_label_hist(const uint64_t* bits, int64_t words, const int32_t* rows, int32_t k, const int32_t* sem,
                    int64_t n_vox, int32_t n_class, int32_t* labels, void* stream);
 
@@ -585,7 +588,9 @@ int b2m_mask_hist(const uint64_t* bits, int64_t words, int32_t k, const int32_t*
 
 /* Gather bits through an index (vox2point) into a byte mask: out[r*n_pts + p] = bit index[p] of row rows[r]
  * (rows NULL = identity, index NULL = identity).
- * Replaces pred_masks[:, vox2point], models/detection_net.py:469-471. */
+ * Replaces pred_masks[:, vox2point], models/detection_net.py:469-471.  A single scene runs the body of
+ * b2m_mask_gather_batch, its descriptor by value: when n_pts is a multiple of 4 the rows are written in 4-byte words, so
+ * `out` must be 4-byte aligned (here and in field 17 of the batched table). */
 int b2m_mask_gather(const uint64_t* bits, int64_t words, const int32_t* rows, int32_t k,
                     const int64_t* index, int64_t n_pts, uint8_t* out, void* stream);
 
