@@ -50,7 +50,10 @@ extern "C" int b2m_set_ious(const float* a, const float* b, int64_t n, float* ou
 // output (each is an elementwise function of the row once the normalisers F = foreground rows and n_valid are known).
 // Sums in fp64 (block tree, then one atomic per block and value).  out[16] doubles:
 //   0 sum |d off|   1 sum |d bounds|   2 sum BCE   3 sum iou   4 sum logit   5 sum iou^2   6 sum logit^2   7 sum iou*logit
-//   8 sum CE        9 correct class   10 (unused)
+//   8 sum CE        9 correct class
+// EX (b2m_detection_loss_ex) adds the IoU loss (model.py:91-129) and the centre-score loss (:179-192) to the same row code:
+//  10 sum (1 - IoU)   11 sum |centre - target|   12 sum target   13 sum centre   14 sum target^2   15 sum centre^2
+//  16 sum target*centre          (target = the row's own L1 offset sum, detached)
 struct LossArgs {
     const float* off; int64_t ld_off; const float* bnd; int64_t ld_bnd; const float* sc; int64_t ld_sc;
     const float* sem; int64_t ld_sem; int C;
@@ -58,11 +61,54 @@ struct LossArgs {
     const uint8_t* fg; const int64_t* gt_sem; int64_t S;
     float w_off, w_bnd, w_sc, w_sem, min_bb; double F; const double* n_valid;
     float* d_off; float* d_bnd; float* d_sc; float* d_sem; int64_t* argmax; double* out;
+    // EX only
+    const float* cs; int64_t ld_cs; float* d_cs; float w_iou, w_cs; int use_iou;
 };
+// d (w_iou / F) * (1 - IoU) / d (offset, bound) of one row, added to g_off / g_bnd; returns 1 - IoU.  The corners are the fp32
+// values torch forms (p = predicted box with clamped bounds, g = true box; [min3, max3]); everything after them is fp64.
+// Conventions at ties are torch autograd's: maximum / minimum of equal corners send half the gradient to each side, a clamped
+// value exactly at its limit (an intersection side of 0, a bound at min_bb_size, a union at the floor) passes the gradient;
+// the union's floor is decided on the fp32 union formed in torch's order.
+__device__ __forceinline__ double iou_loss_row(const float* p, const float* g, const float* pb, float min_bb, double scale,
+                                               double* g_off, double* g_bnd) {
+    double s[3], av[3], wl[3], wh[3];
+    float sf[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float lo = fmax_t(p[j], g[j]), hi = fmin_t(p[3 + j], g[3 + j]);
+        sf[j] = hi - lo;
+        const double raw = (double)hi - (double)lo;
+        s[j] = sf[j] >= 0.f ? raw : 0.0;
+        av[j] = (double)p[3 + j] - (double)p[j];
+        wl[j] = p[j] > g[j] ? 1.0 : (p[j] == g[j] ? 0.5 : 0.0);
+        wh[j] = p[3 + j] < g[3 + j] ? 1.0 : (p[3 + j] == g[3 + j] ? 0.5 : 0.0);
+    }
+    const double inter = (s[0] * s[1]) * s[2], va = (av[0] * av[1]) * av[2];
+    const double vg = (((double)g[3] - (double)g[0]) * ((double)g[4] - (double)g[1])) * ((double)g[5] - (double)g[2]);
+    const double uni = (va + vg) - inter;
+    // the same union in fp32, torch's order: decides the floor
+    const float interf = (clamp0(sf[0]) * clamp0(sf[1])) * clamp0(sf[2]);
+    const float vaf = ((p[3] - p[0]) * (p[4] - p[1])) * (p[5] - p[2]), vgf = ((g[3] - g[0]) * (g[4] - g[1])) * (g[5] - g[2]);
+    const bool open = ((vaf + vgf) - interf) >= 0.000001f;
+    const double den = open ? uni : (double)0.000001f;
+    const double iou = inter / den;
+    const double d_i = open ? (1.0 / den + inter / (den * den)) : 1.0 / den;       // d iou / d inter (union = va + vg - inter)
+    const double d_v = open ? -inter / (den * den) : 0.0;                           // d iou / d va
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int k = (j + 1) % 3, l = (j + 2) % 3;
+        const double di = sf[j] >= 0.f ? s[k] * s[l] : 0.0;                         // d inter / d side j
+        g_off[j] -= scale * d_i * di * (wh[j] - wl[j]);
+        if (pb[j] >= min_bb) g_bnd[j] -= scale * (d_i * di * (wh[j] + wl[j]) + d_v * 2.0 * (av[k] * av[l]));
+    }
+    return 1.0 - iou;
+}
+template <bool EX>
 __global__ __launch_bounds__(256) void detection_loss_kernel(LossArgs a) {
-    __shared__ double red[4][10];
+    constexpr int NV = EX ? 17 : 10;
+    __shared__ double red[4][NV];
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    double v[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[NV] = {};
     if (s < a.S) {
         const bool fg = a.fg == nullptr || a.fg[s] != 0;
         const float inv_f = (float)(1.0 / a.F);
@@ -70,20 +116,43 @@ __global__ __launch_bounds__(256) void detection_loss_kernel(LossArgs a) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) { po[j] = a.off[s * a.ld_off + j]; pb[j] = a.bnd[s * a.ld_bnd + j]; }
         if (fg) {
-            float l_off = 0.f, l_bnd = 0.f, pbox[6], gbox[6];
+            float l_off = 0.f, l_bnd = 0.f, pbox[6], gbox[6], g_off[3], g_bnd[3];
+            double l_off64 = 0.0;                                           // (EX: the centre-score target)
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const float go = a.gt_off[s * 3 + j], gb = a.gt_bnd[s * 3 + j], lc = a.loc[s * 3 + j];
                 const float d0 = po[j] - go, d1 = pb[j] - gb;
                 l_off += fabsf(d0); l_bnd += fabsf(d1);
-                a.d_off[s * 3 + j] = d0 > 0.f ? a.w_off * inv_f : (d0 < 0.f ? -a.w_off * inv_f : 0.f);
-                a.d_bnd[s * 3 + j] = d1 > 0.f ? a.w_bnd * inv_f : (d1 < 0.f ? -a.w_bnd * inv_f : 0.f);
+                g_off[j] = d0 > 0.f ? a.w_off * inv_f : (d0 < 0.f ? -a.w_off * inv_f : 0.f);
+                g_bnd[j] = d1 > 0.f ? a.w_bnd * inv_f : (d1 < 0.f ? -a.w_bnd * inv_f : 0.f);
+                if constexpr (EX) {
+                    const double e0 = (double)po[j] - (double)go;
+                    l_off64 += d0 > 0.f ? e0 : (d0 < 0.f ? -e0 : 0.0);
+                }
                 const float pc = po[j] + lc, gc = go + lc;                  // voted / true centre (model.py:147-150)
                 const float pbc = pb[j] < a.min_bb ? a.min_bb : pb[j];      // torch.clamp(pred_bounds, min=min_bb_size)
                 pbox[j] = pc - pbc; pbox[3 + j] = pc + pbc;
                 gbox[j] = gc - gb; gbox[3 + j] = gc + gb;
             }
             v[0] = l_off; v[1] = l_bnd;
+            if constexpr (EX) {
+                if (a.use_iou) {                                            // model.py:91-129, not detached
+                    double e_off[3] = {g_off[0], g_off[1], g_off[2]}, e_bnd[3] = {g_bnd[0], g_bnd[1], g_bnd[2]};
+                    v[10] = iou_loss_row(pbox, gbox, pb, a.min_bb, (double)a.w_iou / a.F, e_off, e_bnd);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) { g_off[j] = (float)e_off[j]; g_bnd[j] = (float)e_bnd[j]; }
+                }
+                if (a.cs) {                                                 // model.py:179-192: target = this row's L1 offset sum
+                    const float p = a.cs[s * a.ld_cs], d = p - l_off;      // the sign is torch's: fp32 prediction - fp32 target
+                    const double e = (double)p - l_off64;
+                    v[11] = d > 0.f ? e : (d < 0.f ? -e : 0.0);
+                    v[12] = l_off64; v[13] = (double)p; v[14] = l_off64 * l_off64; v[15] = (double)p * (double)p;
+                    v[16] = l_off64 * (double)p;
+                    a.d_cs[s] = d > 0.f ? (float)((double)a.w_cs / a.F) : (d < 0.f ? (float)(-(double)a.w_cs / a.F) : 0.f);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { a.d_off[s * 3 + j] = g_off[j]; a.d_bnd[s * 3 + j] = g_bnd[j]; }
             if (a.sc) {
                 const float iou = box_iou(gbox, pbox);                      // set_IOUs(gt_bbs, pred_bbs)
                 const double x = (double)a.sc[s * a.ld_sc], y = (double)iou;
@@ -95,6 +164,7 @@ __global__ __launch_bounds__(256) void detection_loss_kernel(LossArgs a) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) { a.d_off[s * 3 + j] = 0.f; a.d_bnd[s * 3 + j] = 0.f; }
             if (a.sc) a.d_sc[s] = 0.f;
+            if constexpr (EX) { if (a.cs) a.d_cs[s] = 0.f; }
         }
         if (a.sem) {
             const float* z = a.sem + s * a.ld_sem;
@@ -116,7 +186,7 @@ __global__ __launch_bounds__(256) void detection_loss_kernel(LossArgs a) {
     }
     // block sum in a fixed tree, one atomic per value and block
 #pragma unroll
-    for (int u = 0; u < 10; ++u) {
+    for (int u = 0; u < NV; ++u) {
         double t = v[u];
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) t += __shfl_down(t, d, 64);
@@ -124,19 +194,36 @@ __global__ __launch_bounds__(256) void detection_loss_kernel(LossArgs a) {
     }
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-        for (int u = 0; u < 10; ++u) red[threadIdx.x >> 6][u] = v[u];
+        for (int u = 0; u < NV; ++u) red[threadIdx.x >> 6][u] = v[u];
     }
     __syncthreads();
-    if (threadIdx.x < 10) {
+    if (threadIdx.x < NV) {
         const double t = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
         if (t != 0.0) atomicAdd(a.out + threadIdx.x, t);
     }
 }
 // res[0] total, 1 offset_loss, 2 bounds_loss, 3 bb_score_loss, 4 bb_target_scores, 5 bb_scores_correlation, 6 semantics_loss,
-// 7 semantics_acc
+// 7 semantics_acc;  EX: 8 iou_loss, 9 center_score_loss, 10 center_scores_correlation, 11..15 zero
+// Pearson r of two summed series from their uncentred fp64 sums (n values; sa, sb, saa, sbb, sab).  The centred sums can come
+// out a rounding error below zero for (nearly) constant inputs: clamped before the root (a negative product gave NaN -> +-inf
+// through the floor below).  Zero variance -- all IoUs 0 at a fresh initialisation -- reads 0 here, as model._pearsonr does;
+// scipy.stats.pearsonr returns NaN with a warning for such input.
+// The uncentred form  sum x^2 - (sum x)^2 / n  equals the centred sum only up to the rounding of its two terms, each about
+// (tree depth + blocks) * 2^-53 of sum x^2: for constant input (every score logit equal) it came out as +-1e-13 instead of the
+// exact 0 of  sum (x - mean)^2, and a positive one turned the correlation into ~1e-8 of noise over noise.  A centred sum below
+// that rounding is zero variance (tests/test_gpu_loss.py, case equal_scores)
+__device__ __forceinline__ float pearson_from_sums(double n, int64_t S, double sa, double sb, double saa, double sbb, double sab) {
+    const double ca = saa - sa * sa / n, cb = sbb - sb * sb / n, cab = sab - sa * sb / n;
+    const double noise = (double)((S + 255) / 256 + 16) * 0x1p-52;
+    const double va = ca > noise * saa ? ca : 0.0, vb = cb > noise * sbb ? cb : 0.0;
+    const double den = sqrt(va * vb);
+    return den > 1e-300 ? (float)(cab / den) : 0.f;
+}
+struct LossExFinal { float w_iou, w_cs; int use_iou, has_cs; };
+template <bool EX>
 __global__ void detection_loss_final_kernel(const double* __restrict__ o, double F, const double* __restrict__ n_valid, int64_t S,
                                             float w_off, float w_bnd, float w_sc, float w_sem, int has_sc, int has_sem,
-                                            float* __restrict__ res) {
+                                            LossExFinal x, float* __restrict__ res) {
     const double l_off = o[0] / F, l_bnd = o[1] / F;
     double total = (double)w_off * l_off + (double)w_bnd * l_bnd;
     res[1] = (float)l_off; res[2] = (float)l_bnd;
@@ -145,19 +232,22 @@ __global__ void detection_loss_final_kernel(const double* __restrict__ o, double
         const double bce = o[2] / F;
         total += (double)w_sc * bce;
         res[3] = (float)bce; res[4] = (float)(o[3] / F);
-        const double ca = o[5] - o[3] * o[3] / F, cb = o[6] - o[4] * o[4] / F, cab = o[7] - o[3] * o[4] / F;
-        // Pearson r of (IoU, score logit), a logging value (/root/reference/models/model.py:88).  The centred sums can come out a
-        // rounding error below zero for (nearly) constant inputs: clamped before the root (a negative product gave NaN -> +-inf
-        // through the floor below).  Zero variance -- all IoUs 0 at a fresh initialisation -- reads 0 here, as model._pearsonr
-        // does; scipy.stats.pearsonr returns NaN with a warning for such input
-        // The uncentred form  sum x^2 - (sum x)^2 / F  equals the centred sum only up to the rounding of its two terms, each about
-        // (tree depth + blocks) * 2^-53 of sum x^2: for constant input (every score logit equal) it came out as +-1e-13 instead of
-        // the exact 0 of  sum (x - mean)^2, and a positive one turned the correlation into ~1e-8 of noise over noise.  A
-        // centred sum below that rounding is zero variance (tests/test_gpu_loss.py, case equal_scores)
-        const double noise = (double)((S + 255) / 256 + 16) * 0x1p-52;
-        const double va = ca > noise * o[5] ? ca : 0.0, vb = cb > noise * o[6] ? cb : 0.0;
-        const double den = sqrt(va * vb);
-        res[5] = den > 1e-300 ? (float)(cab / den) : 0.f;
+        res[5] = pearson_from_sums(F, S, o[3], o[4], o[5], o[6], o[7]);        // (IoU, score logit): logging, model.py:88
+    }
+    if constexpr (EX) {
+#pragma unroll
+        for (int u = 8; u < 16; ++u) res[u] = 0.f;
+        if (x.use_iou) {
+            const double l_iou = o[10] / F;
+            total += (double)x.w_iou * l_iou;
+            res[8] = (float)l_iou;
+        }
+        if (x.has_cs) {
+            const double l_cs = o[11] / F;
+            total += (double)x.w_cs * l_cs;
+            res[9] = (float)l_cs;
+            res[10] = pearson_from_sums(F, S, o[12], o[13], o[14], o[15], o[16]);
+        }
     }
     if (has_sem) {
         const double ce = o[8] / *n_valid;
@@ -182,8 +272,35 @@ extern "C" int b2m_detection_loss(const float* off, int64_t ld_off, const float*
     a.w_off = w_off; a.w_bnd = w_bnd; a.w_sc = w_sc; a.w_sem = w_sem; a.min_bb = min_bb_size; a.F = n_fg; a.n_valid = n_valid;
     a.d_off = d_off; a.d_bnd = d_bnd; a.d_sc = d_sc; a.d_sem = d_sem; a.argmax = argmax; a.out = sums;
     B2M_HIP(hipMemsetAsync(sums, 0, 16 * sizeof(double), st));
-    detection_loss_kernel<<<(unsigned)cdiv64(S, 256), 256, 0, st>>>(a);
-    detection_loss_final_kernel<<<1, 1, 0, st>>>(sums, n_fg, n_valid, S, w_off, w_bnd, w_sc, w_sem, sc ? 1 : 0, sem ? 1 : 0, result);
+    detection_loss_kernel<false><<<(unsigned)cdiv64(S, 256), 256, 0, st>>>(a);
+    detection_loss_final_kernel<false><<<1, 1, 0, st>>>(sums, n_fg, n_valid, S, w_off, w_bnd, w_sc, w_sem, sc ? 1 : 0, sem ? 1 : 0,
+                                                        LossExFinal{}, result);
+    B2M_LAUNCH_CHECK();
+    return B2M_OK;
+}
+// b2m_detection_loss plus the IoU loss (use_iou) and the centre-score loss (cs != NULL): the same row code, template flag EX.
+extern "C" int b2m_detection_loss_ex(const float* off, int64_t ld_off, const float* bnd, int64_t ld_bnd, const float* sc, int64_t ld_sc,
+                                     const float* cs, int64_t ld_cs, const float* sem, int64_t ld_sem, int32_t n_class,
+                                     const float* gt_off, const float* gt_bnd, const float* loc, const uint8_t* fg,
+                                     const int64_t* gt_sem, int64_t S, double n_fg, const double* n_valid, float w_off, float w_bnd,
+                                     float w_iou, float w_sc, float w_cs, float w_sem, float min_bb_size, int32_t use_iou,
+                                     float* d_off, float* d_bnd, float* d_sc, float* d_cs, float* d_sem, int64_t* argmax,
+                                     double* sums, float* result, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    B2M_CHECK_ARG(off && bnd && gt_off && gt_bnd && loc && d_off && d_bnd && sums && result && S >= 1 && n_fg >= 1, "bad arguments");
+    B2M_CHECK_ARG(ld_off >= 3 && ld_bnd >= 3 && (!sc || (d_sc && ld_sc >= 1)) && (!cs || (d_cs && ld_cs >= 1)),
+                  "leading dimensions / score gradients");
+    B2M_CHECK_ARG(!sem || (d_sem && argmax && gt_sem && n_valid && n_class >= 1 && ld_sem >= n_class), "semantics arguments");
+    LossArgs a{};
+    a.off = off; a.ld_off = ld_off; a.bnd = bnd; a.ld_bnd = ld_bnd; a.sc = sc; a.ld_sc = ld_sc; a.sem = sem; a.ld_sem = ld_sem;
+    a.C = n_class; a.gt_off = gt_off; a.gt_bnd = gt_bnd; a.loc = loc; a.fg = fg; a.gt_sem = gt_sem; a.S = S;
+    a.w_off = w_off; a.w_bnd = w_bnd; a.w_sc = w_sc; a.w_sem = w_sem; a.min_bb = min_bb_size; a.F = n_fg; a.n_valid = n_valid;
+    a.d_off = d_off; a.d_bnd = d_bnd; a.d_sc = d_sc; a.d_sem = d_sem; a.argmax = argmax; a.out = sums;
+    a.cs = cs; a.ld_cs = ld_cs; a.d_cs = d_cs; a.w_iou = w_iou; a.w_cs = w_cs; a.use_iou = use_iou ? 1 : 0;
+    B2M_HIP(hipMemsetAsync(sums, 0, 32 * sizeof(double), st));
+    detection_loss_kernel<true><<<(unsigned)cdiv64(S, 256), 256, 0, st>>>(a);
+    detection_loss_final_kernel<true><<<1, 1, 0, st>>>(sums, n_fg, n_valid, S, w_off, w_bnd, w_sc, w_sem, sc ? 1 : 0, sem ? 1 : 0,
+                                                       LossExFinal{w_iou, w_cs, use_iou ? 1 : 0, cs ? 1 : 0}, result);
     B2M_LAUNCH_CHECK();
     return B2M_OK;
 }

@@ -1306,11 +1306,7 @@ class _DetectionLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        g0 = g[0]
-        live = [d for d in ctx.grads if d is not None]
-        scaled = iter(torch._foreach_mul(live, g0))         # one launch for the four heads' gradients
-        out = [None if d is None else next(scaled) for d in ctx.grads]
-        return (out[0], out[1], out[2], out[3]) + (None,) * 9
+        return _scaled_grads(ctx.grads, g[0]) + (None,) * 9         # one launch for the four heads' gradients
 
 
 def detection_loss(off, bnd, sc, sem, gt_off, gt_bnd, loc, fg_u8, gt_sem, n_fg, n_valid, weights, min_bb):
@@ -1324,6 +1320,98 @@ def detection_loss(off, bnd, sc, sem, gt_off, gt_bnd, loc, fg_u8, gt_sem, n_fg, 
         # (the argmax rides on the context of the node that made `res`; without autograd the kernel's buffer is re-made)
         argmax = node.argmax if node is not None and hasattr(node, 'argmax') else torch.argmax(sem.detach(), 1)
     return res, argmax
+
+
+def _f32rows(t):
+    """A (rows, width) head output as the loss entries read it: fp32, unit stride along a row, any row pitch >= width.  A column
+    window of a wider tensor goes through as it is (its stride(0) is the entry's ld); anything else is compacted."""
+    if t.dtype == torch.float32 and t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1) and t.stride(0) >= t.shape[1]:
+        return t
+    return _f32c(t)
+
+
+class _DetectionLossEx(torch.autograd.Function):
+    """_DetectionLoss plus the IoU loss (model.py:91-129) and the centre-score loss (:179-192): b2m_detection_loss_ex, the same
+    row code.  Returns the 16 result floats (include/b2m.h); element 0 is the weighted total and the only one gradients flow
+    through.  `weights` = (offsets, bounds, iou, scores, centre, semantics)."""
+
+    @staticmethod
+    def forward(ctx, off, bnd, sc, cs, sem, gt_off, gt_bnd, loc, fg_u8, gt_sem, n_fg, n_valid, weights, min_bb, use_iou):
+        off, bnd = _f32rows(off), _f32rows(bnd)
+        sc, cs, sem = (_f32rows(t) if t is not None else None for t in (sc, cs, sem))
+        S, dev = off.shape[0], off.device
+        d_off, d_bnd = torch.empty((S, 3), device=dev), torch.empty((S, 3), device=dev)
+        d_sc = torch.empty((S, 1), device=dev) if sc is not None else None
+        d_cs = torch.empty((S, 1), device=dev) if cs is not None else None
+        C = sem.shape[1] if sem is not None else 0
+        d_sem = torch.empty((S, C), device=dev) if sem is not None else None
+        argmax = torch.empty(S, dtype=torch.int64, device=dev) if sem is not None else None
+        sums = torch.empty(32, dtype=torch.float64, device=dev)
+        result = torch.empty(16, dtype=torch.float32, device=dev)
+        ld = lambda t: t.stride(0) if t is not None else 0
+        _call('b2m_detection_loss_ex', off.data_ptr(), off.stride(0), bnd.data_ptr(), bnd.stride(0), _ptr(sc), ld(sc), _ptr(cs),
+              ld(cs), _ptr(sem), ld(sem), C, gt_off.data_ptr(), gt_bnd.data_ptr(), loc.data_ptr(), _ptr(fg_u8), _ptr(gt_sem), S,
+              float(n_fg), _ptr(n_valid), weights[0], weights[1], weights[2], weights[3], weights[4], weights[5], min_bb,
+              1 if use_iou else 0, d_off.data_ptr(), d_bnd.data_ptr(), _ptr(d_sc), _ptr(d_cs), _ptr(d_sem), _ptr(argmax),
+              sums.data_ptr(), result.data_ptr())
+        ctx.grads = (d_off, d_bnd, d_sc, d_cs, d_sem)
+        ctx.argmax = argmax
+        return result
+
+    @staticmethod
+    def backward(ctx, g):
+        return _scaled_grads(ctx.grads, g[0]) + (None,) * 10
+
+
+class _RowsCELoss(torch.autograd.Function):
+    """Cross entropy over the rows of the per-voxel semantics head, values and gradient in one pass (b2m_rows_ce_loss;
+    model.py:212-223).  Returns 3 floats: weight * loss (the only one gradients flow through), loss, accuracy."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, n_valid, weight):
+        logits = _f32rows(logits)
+        N, C = logits.shape
+        dev = logits.device
+        d_logits = torch.empty((N, C), device=dev)
+        argmax = torch.empty(N, dtype=torch.int64, device=dev)
+        partial = torch.empty(2 * ((N + 255) // 256), dtype=torch.float64, device=dev)
+        result = torch.empty(3, dtype=torch.float32, device=dev)
+        _call('b2m_rows_ce_loss', logits.data_ptr(), logits.stride(0), N, C, labels.data_ptr(), n_valid.data_ptr(), weight,
+              d_logits.data_ptr(), argmax.data_ptr(), partial.data_ptr(), result.data_ptr())
+        ctx.grads = (d_logits,)
+        ctx.argmax = argmax
+        return result
+
+    @staticmethod
+    def backward(ctx, g):
+        return _scaled_grads(ctx.grads, g[0]) + (None,) * 3
+
+
+def _scaled_grads(grads, g0):
+    """The stored gradients of the present heads times the incoming gradient: one launch."""
+    live = [d for d in grads if d is not None]
+    scaled = iter(torch._foreach_mul(live, g0))
+    return tuple(None if d is None else next(scaled) for d in grads)
+
+
+def _node_argmax(res, logits):
+    # (the argmax rides on the context of the node that made `res`; without autograd the kernel's buffer is re-made)
+    node = res.grad_fn
+    return node.argmax if node is not None and hasattr(node, 'argmax') else torch.argmax(logits.detach(), 1)
+
+
+def detection_loss_ex(off, bnd, sc, cs, sem, gt_off, gt_bnd, loc, fg_u8, gt_sem, n_fg, n_valid, weights, min_bb, use_iou):
+    """-> (result (16,) float tensor: the 8 values of detection_loss, then iou_loss, center_score_loss, center_scores_correlation,
+    5 zeros;  predicted class per row or None).  `cs` None = no centre head or the term not active yet."""
+    res = _DetectionLossEx.apply(off, bnd, sc, cs, sem, gt_off, gt_bnd, loc, fg_u8, gt_sem, n_fg, n_valid, weights, min_bb, use_iou)
+    return res, (_node_argmax(res, sem) if sem is not None else None)
+
+
+def rows_ce_loss(logits, labels, n_valid, weight):
+    """-> (result (3,) float tensor: weight * loss, loss, accuracy = hits / rows;  predicted class per row).  `labels` int64 on
+    the device of `logits` (outside [0, n_class): ignored), `n_valid` a float64 device scalar (1,) = the rows that count."""
+    res = _RowsCELoss.apply(logits, labels, n_valid, float(weight))
+    return res, _node_argmax(res, logits)
 
 
 def fused_loss_enabled() -> bool:

@@ -263,15 +263,17 @@ class Model:
         return losses_dict, pred
 
     def _fused_losses(self, batch, pred, epoch, fg, fg_rows, on_fg):
-        """The ScanNet loss configuration (offsets + bounds [+ IoU-target scores] [+ semantics] on the foreground segments)
-        as ONE launch for values and gradients (functional.detection_loss) instead of ~150 elementwise torch launches between
-        the forward and the backward pass; None for every other configuration (IoU loss, centre scores, per-voxel semantics:
-        the term-by-term code below).  Same keys, same values (tests/test_gpu_net.py::test_losses_match_reference_golden)."""
+        """Every loss configuration with the offsets and bounds heads as one launch for the values and gradients of the
+        segment-level terms (functional.detection_loss; with the IoU loss or the centre head functional.detection_loss_ex) plus
+        one for the per-voxel head (functional.rows_ce_loss), instead of ~150 elementwise torch launches between the forward and
+        the backward pass.  None -- the term-by-term code above -- with B2M_FUSED_LOSS=0, without a row to average over, for a
+        head set without offsets or bounds, and for the one combination the reference cannot evaluate either (centre head on
+        masked rows without loss_on_fg_instances: the shape mismatch at model.py:182-186 is raised there as before).  Same keys,
+        same values (tests/test_gpu_net.py::test_losses_match_reference_golden)."""
         from . import functional as F_
         cfg, device = self.cfg, self.device
         heads = cfg.network_heads
-        if not F_.fused_loss_enabled() or cfg.use_bb_iou_loss or cfg.mlp_center_scores in heads or \
-                cfg.mlp_per_vox_semantics in heads or cfg.mlp_offsets not in heads or cfg.mlp_bounds not in heads:
+        if not F_.fused_loss_enabled() or cfg.mlp_offsets not in heads or cfg.mlp_bounds not in heads:
             return None
         if on_fg and (fg is None or fg_rows is None):
             return None
@@ -279,8 +281,11 @@ class Model:
         n_fg = int(fg_rows.shape[0]) if on_fg else S
         if S == 0 or n_fg == 0:
             return None
+        has_cs = cfg.mlp_center_scores in heads and epoch >= cfg.mlp_center_scores_start_epoch
+        if has_cs and on_fg and not cfg.loss_on_fg_instances:
+            return None
         f32 = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
-        has_sc, has_sem = cfg.mlp_bb_scores in heads, cfg.mlp_semantics in heads
+        has_sc, has_sem, has_vox = cfg.mlp_bb_scores in heads, cfg.mlp_semantics in heads, cfg.mlp_per_vox_semantics in heads
         w_sc = 0.0
         if has_sc:
             w_sc = float(cfg.loss_weight_bb_scores) if epoch >= cfg.mlp_bb_scores_start_epoch else 0.0
@@ -288,22 +293,41 @@ class Model:
         if has_sem:
             gt_sem = self._sem_lut()[batch['gt_semantics'].to(device)].contiguous()
             n_valid = (gt_sem >= 0).sum(dtype=torch.float64).reshape(1)
-        res, argmax = F_.detection_loss(
-            pred[cfg.mlp_offsets], pred[cfg.mlp_bounds], pred[cfg.mlp_bb_scores] if has_sc else None,
-            pred[cfg.mlp_semantics] if has_sem else None, f32(batch['gt_bb_offsets']), f32(batch['gt_bb_bounds']),
-            f32(batch['input_location']), fg.to(torch.uint8).contiguous() if on_fg else None, gt_sem, n_fg, n_valid,
-            (float(cfg.loss_weight_bb_offsets), float(cfg.loss_weight_bb_bounds), w_sc, float(cfg.loss_weight_semantics)),
-            float(cfg.min_bb_size))
+        sc, sem = pred[cfg.mlp_bb_scores] if has_sc else None, pred[cfg.mlp_semantics] if has_sem else None
+        fixed = (f32(batch['gt_bb_offsets']), f32(batch['gt_bb_bounds']), f32(batch['input_location']),
+                 fg.to(torch.uint8).contiguous() if on_fg else None, gt_sem, n_fg, n_valid)
+        w_off, w_bnd, w_sem = float(cfg.loss_weight_bb_offsets), float(cfg.loss_weight_bb_bounds), float(cfg.loss_weight_semantics)
+        if cfg.use_bb_iou_loss or has_cs:
+            res, argmax = F_.detection_loss_ex(
+                pred[cfg.mlp_offsets], pred[cfg.mlp_bounds], sc, pred[cfg.mlp_center_scores] if has_cs else None, sem, *fixed,
+                (w_off, w_bnd, float(cfg.loss_weight_bb_iou) if cfg.use_bb_iou_loss else 0.0, w_sc,
+                 float(cfg.loss_weight_center_scores) if has_cs else 0.0, w_sem), float(cfg.min_bb_size), bool(cfg.use_bb_iou_loss))
+        else:
+            res, argmax = F_.detection_loss(pred[cfg.mlp_offsets], pred[cfg.mlp_bounds], sc, sem, *fixed,
+                                            (w_off, w_bnd, w_sc, w_sem), float(cfg.min_bb_size))
         d = res.detach()
         out = {'optimization_loss': res[0], 'offset_loss': d[1], 'bounds_loss': d[2]}
+        if cfg.use_bb_iou_loss:
+            out['iou_loss'] = d[8]
         if has_sc:
             out['bb_scores_correlation'] = d[5]
             out['bb_score_loss'] = d[3]
             out['bb_target_scores'] = d[4]
+        if has_cs:
+            out['center_score_loss'] = d[9]
+            out['center_scores_correlation'] = d[10]
         if has_sem:
             out['semantics_loss'] = d[6]
             out['semantics_acc'] = d[7]
             out['semantics_mIoU'] = _LazyMean(argmax, gt_sem)
+        if has_vox:                                              # model.py:212-223, over the voxel rows
+            gt_vox = self._sem_lut()[batch['gt_per_vox_semantics'].to(device)].contiguous()
+            vox, _ = F_.rows_ce_loss(pred[cfg.mlp_per_vox_semantics], gt_vox, (gt_vox >= 0).sum(dtype=torch.float64).reshape(1),
+                                     float(cfg.loss_weight_per_vox_semantics))
+            out['optimization_loss'] = out['optimization_loss'] + vox[0]
+            dv = vox.detach()
+            out['per_vox_semantics_loss'] = dv[1]
+            out['per_vox_semantics_acc'] = dv[2]
         return out
 
     def get_prediction(self, batch, with_grad=False, to_cpu=True, min_size=True, get_all=False):

@@ -135,7 +135,7 @@ int b2m_rulebook_balance(int32_t* rb_cnt, int32_t K, int64_t n_out, void* stream
 int b2m_rulebook(const int32_t* nbr, int64_t ld, int32_t K, int64_t n_out,
                  int32_t* rb_in, uint8_t* rb_out, int32_t* rb_cnt, int32_t* pair_total, void* stream);
 
-/* Detection losses of the ScanNet configuration, values AND gradients in one pass over the prediction rows
+/* Detection losses (offsets + bounds [+ scores] [+ segment semantics]: the ScanNet configuration), values AND gradients in one pass over the prediction rows
  * (/root/reference/models/model.py:62-88, 133-176, 194-210; replaces ~150 elementwise torch launches per step):
  *   offset_loss = mean_fg sum_j |off - gt_off|, bounds_loss likewise, bb_score_loss = BCEWithLogits(score, IoU(gt box, predicted
  *   box with bounds clamped at min_bb_size)) over the foreground rows, semantics_loss = CrossEntropy(sem, gt_sem; ignore < 0 or
@@ -151,6 +151,34 @@ int b2m_detection_loss(const float* off, int64_t ld_off, const float* bnd, int64
                        const double* n_valid, float w_off, float w_bnd, float w_sc, float w_sem, float min_bb_size,
                        float* d_off, float* d_bnd, float* d_sc, float* d_sem, int64_t* argmax, double* sums,
                        float* result, void* stream);
+/* The same pass with the two remaining segment-level terms of the reference (same row code, one more template flag):
+ *   use_iou != 0: iou_loss = mean_fg (1 - IoU(predicted box with bounds clamped at min_bb_size, true box)), union floored at
+ *     float32(1e-6) (model.py:91-129).  NOT detached: its gradient w.r.t. offsets and bounds is added to the L1 gradients of the
+ *     row; a bound below min_bb_size gets none.  Corners in fp32 in torch's order, derivative and sums in fp64; at ties torch
+ *     autograd's conventions (equal corners under max / min: half each; an intersection side of exactly 0, a bound exactly at
+ *     min_bb_size, a union exactly at the floor: the gradient passes).
+ *   cs != NULL: center_score_loss = mean_fg |cs - t|, t = the row's own L1 offset sum, detached (model.py:179-192); the sign is
+ *     that of the fp32 difference; d_cs (S) is the gradient w.r.t. the (S,1) centre head.  The caller passes NULL while the term
+ *     is not active (epoch < mlp_center_scores_start_epoch): the head then gets no gradient.
+ * total = w_off * offset + w_bnd * bounds + w_iou * iou + w_sc * score + w_cs * centre + w_sem * semantics.
+ * sums: double[32] scratch; result: float[16] = the 8 values of b2m_detection_loss, then 8 iou_loss, 9 center_score_loss,
+ * 10 center_scores_correlation (Pearson of t and cs, zero variance reads 0), 11..15 zero. */
+int b2m_detection_loss_ex(const float* off, int64_t ld_off, const float* bnd, int64_t ld_bnd, const float* sc, int64_t ld_sc,
+                          const float* cs, int64_t ld_cs, const float* sem, int64_t ld_sem, int32_t n_class,
+                          const float* gt_off, const float* gt_bnd, const float* loc, const uint8_t* fg,
+                          const int64_t* gt_sem, int64_t S, double n_fg, const double* n_valid, float w_off, float w_bnd,
+                          float w_iou, float w_sc, float w_cs, float w_sem, float min_bb_size, int32_t use_iou,
+                          float* d_off, float* d_bnd, float* d_sc, float* d_cs, float* d_sem, int64_t* argmax,
+                          double* sums, float* result, void* stream);
+/* Cross entropy over the rows of the per-voxel semantics head (model.py:212-223), values and gradient in one pass:
+ * logits (N, n_class) with row pitch ld, 1 <= n_class <= 63; labels int64 (N), those outside [0, n_class) are ignored; n_valid:
+ * device scalar = rows with a valid label (0: the loss is NaN and the gradient 0, as torch's).  d_logits: dense (N, n_class)
+ * gradient of weight * loss; argmax (N): first maximum of every row; partial: double[2 * ceil(N / 256)] scratch, one slot pair
+ * per workgroup, added in a fixed order (no floating-point atomics: the same inputs give the same bits);
+ * result: float[3] = weight * loss, loss, accuracy = hits / N. */
+int b2m_rows_ce_loss(const float* logits, int64_t ld, int64_t N, int32_t n_class, const int64_t* labels,
+                     const double* n_valid, float weight, float* d_logits, int64_t* argmax, double* partial,
+                     float* result, void* stream);
 
 /* ---------------------------------------------------------------- sparse convolution (fp32, MFMA) */
 
