@@ -145,6 +145,10 @@ PROTOTYPES = {
     'b2m_ap_rows': [P, I32, I32, P],
     'b2m_ap_match': [P, I32, I64, P, P, P, I32, P, I64, P, P, P, I64, P, P, P, I32, P],
     'b2m_ap_curve': [P, I64, P, P, I32, P, I64, I64, P, P, P, P],
+    # ... mesh over-segmentation (box2mask_amd/oversegment.py)
+    'b2m_mesh_edge_weights': [P, I32, I64, I64, P],
+    'b2m_edge_sort_keys': [P, I64, P, I64, P],
+    'b2m_graph_segment': [P, I32, I64, I64, F32, I32, I32, P],
 }
 PLAIN = {'b2m_last_error': (C.c_char_p, []), 'b2m_version': (C.c_int, []), 'b2m_device_ok': (C.c_int, []),
          'b2m_reload_env': (C.c_int, []),

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libb2m_hip.so')
 SOURCES = ['coords.hip', 'conv.hip', 'norm.hip', 'nms.hip', 'voxelize.hip', 'xchg.hip', 'detbox.hip', 'cluster.hip', 'augment.hip',
-           'neighbors.hip', 'apmatch.hip', 'guard.hip', 'loss.hip']
+           'neighbors.hip', 'apmatch.hip', 'guard.hip', 'loss.hip', 'overseg.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-munsafe-fp-atomics', '-Wall',
          '-Wno-unused-function']

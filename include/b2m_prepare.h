@@ -204,6 +204,41 @@ int b2m_nn_build(const double* ref, int64_t n_ref, void* workspace, void* stream
 int b2m_nn_query(const double* ref, int64_t n_ref, const void* workspace, const double* q, int64_t n_q, int32_t* idx,
                  double* dist, void* stream);
 
+/* ---- mesh over-segmentation (box2mask_amd/oversegment.py, csrc/overseg.hip): the Felzenszwalb graph segmentation the reference
+ * runs over a mesh's faces (dataprocessing/oversegmentation/cpp/segmentator.cpp) to make the `segments` every scene starts from, by
+ * the rule of profiles/overseg_rule.md.  fp32 throughout, no contraction, correctly rounded division and square root.  All scenes of
+ * a batch go through one table: `desc` = device array of n_scenes records of B2M_OVERSEG_DESC int64 fields (pointers as integers):
+ *    0 pos (float*, V x 3)            1 V                          2 faces (int64*, F x 3)        3 F
+ *    4 row_ptr (int64*, V + 1)        5 face_of (int64*, 3F): the vertex-to-face CSR, a row ascending in 3f + slot
+ *    6 normals (float*, V x 3, out)   7 weights (float*, E)        8 keys (uint64*, n_pad)        9 n_pad (power of two >= max(E, 2))
+ *   10 edge_a (int32*, E)            11 edge_b (int32*, E)        12 E (= 3F for a mesh)
+ *   13 parent  14 rank  15 size (int32*, V each)   16 thr (float*, V): the forest, scratch
+ *   17 seg (int64*, V, out)          18 out (int32*, 4: n_segments, n_nan, error flag, spare)     19 spare
+ * Each entry reads only the fields of its half.  V < 2^31, n_pad < 2^31 (the limit of b2m_sort_u64). ---- */
+#define B2M_OVERSEG_DESC 20
+
+/* First half.  normals[v] = the running mean of the unit normals of v's faces in face order (t = 1 / (count + 1),
+ * normal = t * n_f + (1 - t) * normal; never renormalised; a vertex no face names keeps 0), segmentator.cpp:107-116, 203-207.
+ * Edge e = 3f + slot joins (i1,i2), (i1,i3), (i3,i2) of face f (:197-200); weights[e] = 1 - n_a . n_b, squared when n_b . d > 0 with
+ * d the unit vector from a to b (:211-229); keys[e] = code(w) << 32 | e with an order-preserving code in which -0 == +0 and a NaN
+ * comes after every other value; keys[E .. n_pad) = 2^64-1.  Faces whose indices lie outside [0, V) contribute to no normal and give
+ * the edge (0,0) a NaN weight (the wrapper refuses them).  max_vert / max_pad: the largest V / n_pad of the table. */
+int b2m_mesh_edge_weights(const int64_t* desc, int32_t n_scenes, int64_t max_vert, int64_t max_pad, void* stream);
+
+/* keys[e] = code(weights[e]) << 32 | e for e < n_edges, 2^64-1 up to n_pad: the keys of the first half for caller-made weights. */
+int b2m_edge_sort_keys(const float* weights, int64_t n_edges, uint64_t* keys, int64_t n_pad, void* stream);
+
+/* Second half, over keys sorted by b2m_sort_u64 (the (w, e) order).  stages & 1: parent = self, rank 0, size 1, thr = k_thresh, then
+ * pass one (segment_graph, :71-92): for every edge in order, A = find(a), B = find(b); A != B && w <= thr[A] && w <= thr[B] joins
+ * them by rank (:43-54) and sets thr[root] = w + k_thresh / size(root).  stages & 2: pass two (:237-243) over the SAME sorted edges:
+ * A != B && (size(A) < seg_min_verts || size(B) < seg_min_verts) joins.  stages & 4: seg[v] = find(v) (root vertex ids, not dense
+ * ranks), out[0] = number of roots, out[1] = number of NaN weights.  One wave per scene runs the two passes (a window of 64 edges at
+ * a time, resolved in lane order in registers); the results are those of the sequential loop.  The edges need not come from a mesh.
+ * A find that has not reached a root after 64 hops (union by rank allows 31), an endpoint outside [0, V) or a key that names no
+ * edge sets out[2] and ends the scene's passes; the wrapper raises.  No synchronisation, no host read. */
+int b2m_graph_segment(const int64_t* desc, int32_t n_scenes, int64_t max_vert, int64_t max_edges, float k_thresh,
+                      int32_t seg_min_verts, int32_t stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
